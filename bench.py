@@ -9,7 +9,13 @@ K=131072, nbits=2), index and queries already resident in HBM.  The steps ROTATE
 sharded by passage (BASELINE.json configs[3]); the total work is fixed, so `scaling` is "strong".  Rank 0 prints ONE JSON
 line.
 
-Besides the contract's keys the line carries (N = 1):
+A plain run sets up, warms up, times the K steps and prints the line: the contract's keys (`value` = queries/sec of the
+timed steps, `ms_per_step` = milliseconds per timed step), `recall_at_5` of the last step of each batch, the index build time
+and the workspace size.  `--dump-outputs DIR` then also writes what the last timed step returned -- DIR/pids.npy (float64,
+-1 padded), DIR/scores.npy (float32, 0 padded) and DIR/counts.npy (float64), [batch, k] / [batch] -- from inputs that are
+the same on every run with the same arguments.  Everything else is measured only with `--full`.
+
+With `--full` the line also carries (N = 1):
   roofline      the dominant kernel (largest per-stage HIP-event time inside the timed region) against its roof, from the
                 kernel's OWN compulsory bytes / flops (SURVEY 8(d) counts intermediates as 0); `per_kernel` does the same
                 for every stage; `whole_path` = the bytes this build must move per query against the HBM peak;
@@ -17,7 +23,8 @@ Besides the contract's keys the line carries (N = 1):
                 a second sample on 8 threads, with the ranked lists compared to the GPU's in the same run;
   sub_results   the same path at k=5, nbits=8, ragged passages and Nq=832 (short runs);
   hbm_copy_GBs  measured device copy bandwidth (read + write), next to the 8 TB/s spec used as `peak`.
-N > 1: `exchange_ms` = wall time of each collective of the exact sharded protocol, measured in separate un-timed steps.
+N > 1 with `--full`: `exchange_ms` = wall time of each collective of the exact sharded protocol, measured in separate
+un-timed steps, and the fast and replica modes timed beside the one asked for.
 """
 import argparse
 import json
@@ -71,7 +78,23 @@ def parse():
     ap.add_argument("--force-distributed", action="store_true",
                     help="N = 1 only: run the sharded protocol (one shard) with its collectives issued through RCCL anyway -- "
                          "checks the torch.distributed / RCCL call path (dtypes, layouts) on a 1-GPU box")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-stage events and roofline, CPU baseline, sub-results, "
+                         "latency / PCIe / API-layer rates (N = 1), exchange timings and the other shard modes (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/{pids,scores,counts}.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(out_dir, p, s, c):
+    """The arrays a caller of search_batch receives, as float64 (ids, counts: exact) / float32 (scores) .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, dt in (("pids", p, np.float64), ("scores", s, np.float32), ("counts", c, np.float64)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(dt))
 
 
 def self_launch(args):
@@ -276,11 +299,13 @@ def main():
         args.shard_depth = 1 if (cal[1] <= cal[2] or args.batch <= args.sub_batch) else 2
         shard_calibration = {"ms_per_step_depth1": cal[1], "ms_per_step_depth2": cal[2], "chosen_depth": args.shard_depth}
     dt, _, recall5, last = timed(scorer, Qs, tgts, k, (ncells, thr, ndocs), args.steps, args.warmup, collect_stages=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last[(args.steps - 1) % nb])
     # Per-stage HIP events (the roofline's kernel durations) come from a second pass over the same K steps: ten timing
     # events per native call cost 1.5 % of a step at one call per step and 6 % at four sub-batches (profiles/README.md),
     # so they stay out of the pass `value` is taken from; the instrumented pass's own step time is reported beside them.
     stage_ms, ms_per_step_events = {}, None
-    if not exact and not os.environ.get('BENCH_NO_EVENTS'):
+    if args.full and not exact and not os.environ.get('BENCH_NO_EVENTS'):
         dt_ev, stage_ms, _, _ = timed(scorer, Qs, tgts, k, (ncells, thr, ndocs), args.steps, 1, collect_stages=True)
         ms_per_step_events = dt_ev / args.steps * 1e3
     ms_per_step = dt / args.steps * 1e3
@@ -288,7 +313,7 @@ def main():
 
     # ---- N > 1: wall time of every collective of the exact protocol, in separate un-timed steps ------------------------
     exchange_ms = None
-    if exact:
+    if args.full and exact:
         sharded.timings = {}   # every exchange then runs synchronously between two events on the launch stream (no host sync inside)
         nprobe = 3
         for i in range(nprobe):
@@ -312,7 +337,7 @@ def main():
     # ---- N > 1, exact mode: the FAST mode beside it (north_star's collective: every shard runs S0..S4, ONE all-gather of the
     # per-shard top-k lists, merged) -- same steps, same queries, timed the same way ---------------------------------------
     fast_line = None
-    if exact:
+    if args.full and exact:
         exact = False
         try:
             dt_f, _, recall_f, _ = timed(scorer, Qs, tgts, k, (ncells, thr, ndocs), args.steps, 2, collect_stages=False)
@@ -330,7 +355,7 @@ def main():
     # whenever the index fits one HBM (a 1 M-passage index is 7 GB, the 6 M one 37 GB of 288 GB); sharding is for indexes
     # larger than one HBM and for latency -------------------------------------------------------------
     replica_line = None
-    if use_dist and world > 1:
+    if args.full and use_dist and world > 1:
         try:
             def build_whole():
                 return synth.make_corpus(args.passages, doclen, K, args.nbits, seed=0, device="cuda")
@@ -382,7 +407,7 @@ def main():
             replica_line = {"failed": repr(e)}
 
     out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- workload statistics of the last batch (outside the timed region) ----------------------------------------
         sub_n = min(args.batch, args.sub_batch)
         nlast = (args.batch - 1) % sub_n + 1   # taps index into the last native call: never more queries than its smallest sub-batch
@@ -495,6 +520,7 @@ def main():
                                "frac_of_hbm_peak": alg_build * qps / 1e9 / HBM_PEAK_GBS,
                                "reference_formulation_bytes_per_query": alg_ref}}
 
+    if rank == 0:
         out = {
             "metric": "queries/sec", "value": qps, "unit": "queries/sec", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
@@ -506,12 +532,14 @@ def main():
                                    f"{nb} query batches in rotation",
                        "parallelism": (f"index sharded by passage over {world} GPUs, " + (("stage 0 replicated, " if args.replicate_stage0 else "stage 0 split by query + exchange of idx bitsets/cells, ") + "all-gather of stage-1 keys + SUM all-reduces of slot-aligned stage-2/3 keys, result identical to the unsharded index" if exact else "all-gather of per-shard top-k")) if world > 1 else "1 GPU",
                        "queries_per_step": args.batch, "sub_batch": min(args.batch, args.sub_batch), "streams": args.streams},
-            "recall_at_5": recall5, "roofline": roof, "cpu_baseline": None, "stage_ms_per_step": stage_ms,
+            "recall_at_5": recall5,
             "toolchain": _native.toolchain().splitlines(),   # the compiler the loaded library was built with
-            "ms_per_step_with_stage_events": ms_per_step_events,
-            "candidates_per_query": P_mean, "cells_per_query": ncell_mean,
-            "hbm_copy_GBs": copy_gbs, "index_build_s": t_build, "workspace_GB": scorer.workspace_bytes() / 1e9,
+            "index_build_s": t_build, "workspace_GB": scorer.workspace_bytes() / 1e9,
         }
+        if args.full:
+            out.update({"roofline": roof, "cpu_baseline": None, "stage_ms_per_step": stage_ms,
+                        "ms_per_step_with_stage_events": ms_per_step_events,
+                        "candidates_per_query": P_mean, "cells_per_query": ncell_mean, "hbm_copy_GBs": copy_gbs})
         if shard_calibration is not None:
             out["shard_pipeline"] = shard_calibration
         if fast_line is not None:
@@ -526,7 +554,7 @@ def main():
                                        "ms_per_step_unpipelined is the same step as ONE protocol call per rank")
 
     # ---- CPU baseline (rank 0, N=1 only): the reference's own C++ stages + torch-CPU glue, bounded samples ----------------
-    if rank == 0 and not use_dist and not args.no_cpu_baseline and args.cpu_queries > 0:
+    if rank == 0 and args.full and not use_dist and not args.no_cpu_baseline and args.cpu_queries > 0:
         try:
             from oracle import oracle as orc
             arrays = synth.corpus_to_arrays(corpus)
@@ -637,7 +665,7 @@ def main():
             out["cpu_baseline"] = {"value": None, "unit": "queries/sec", "cores": 0, "kind": "port", "sample": f"failed: {e!r}"}
 
     # ---- sub-results (N = 1): the same path at the other operating points SURVEY 8(d) names -----------------------------
-    if rank == 0 and not use_dist and not args.no_extras:
+    if rank == 0 and args.full and not use_dist and not args.no_extras:
         subs = []
 
         def sub_roofline(sc, st_, pol, nq_full, nbits_, queries_per_step):

@@ -22,7 +22,7 @@ def test_bench_two_ranks_on_one_device(mode):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-device-smoke", "--shard-mode", mode,
            "--passages", "40000", "--doclen", "64", "--batch", "128", "--sub-batch", "64", "--query-batches", "2",
-           "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-built-index"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--no-built-index"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
