@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FLMR_ABI_VERSION 5
+#define FLMR_ABI_VERSION 6
 
 typedef enum flmr_status {
     FLMR_OK = 0,
@@ -365,6 +365,15 @@ int flmr_nearest_centroids(const float* centroids, int64_t K, const float* emb, 
                            flmr_stream_t stream);
 int flmr_compress_residuals(const float* centroids, int64_t K, const float* emb, const int32_t* codes, int64_t n,
                             const float* bucket_cutoffs, int32_t nbits, uint8_t* out_residuals, flmr_stream_t stream);
+/*   flmr_compress_f16       both of the above in one pass for fp16 token rows (what encoders emit; the reference's GPU codec
+ *                           rounds the batch to half before its argmax, residual.py:169-176): centroids_f16 [K,128] and
+ *                           emb_f16 [n,128] are IEEE half bit patterns (16-byte aligned), out_codes i32 [n] = argmax_c of the
+ *                           fp32-accumulated dot product (fp16 products are exact in fp32; lowest c on exact ties; subnormal
+ *                           fp16 inputs count), out_residuals u8 [n, 16*nbits] (8-byte aligned) = the bytes
+ *                           flmr_compress_residuals writes for float(emb) with those codes.  nbits outside {1,2,4,8} ->
+ *                           FLMR_ERR_UNSUPPORTED.  Workspace K x 256 B (independent of n); synchronises `stream`. */
+int flmr_compress_f16(const uint16_t* centroids_f16, int64_t K, const uint16_t* emb_f16, int64_t n, const float* bucket_cutoffs,
+                      int32_t nbits, int32_t* out_codes, uint8_t* out_residuals, flmr_stream_t stream);
 /*   flmr_build_ivf          the inverted file of an index: for every centroid the ascending unique pids of the passages that
  *                           hold a token assigned to it -- optimize_ivf, TPC/indexing/utils.py:8-53 (codes.sort() of
  *                           collection_indexer.py:388-426, embedding id -> pid, unique per centroid).  codes i32 [n_tokens] in

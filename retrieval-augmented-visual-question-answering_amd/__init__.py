@@ -13,7 +13,8 @@ from .index import DeviceIndex, IndexArrays, codec_tables, load_index_arrays
 
 __all__ = ["ColBERTConfig", "RunConfig", "Run", "Queries", "Ranking", "Collection", "Provenance", "IndexArrays",
            "DeviceIndex", "load_index_arrays", "codec_tables", "build_native", "FlmrNativeError", "Searcher",
-           "IndexScorer", "install", "uninstall", "installed", "Indexer", "FLMRModelForRetrieval"]
+           "IndexScorer", "install", "uninstall", "installed", "Indexer", "FLMRModelForRetrieval", "ChunkedIndexBuilder",
+           "chunks_of_rank"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported lazily
@@ -26,6 +27,9 @@ def __getattr__(name):  # torch-dependent pieces are imported lazily
     if name == "Indexer":
         from .indexer import Indexer
         return Indexer
+    if name in ("ChunkedIndexBuilder", "chunks_of_rank"):
+        from . import indexing
+        return getattr(indexing, name)
     if name == "FLMRModelForRetrieval":
         from .flmr import FLMRModelForRetrieval
         return FLMRModelForRetrieval

@@ -12,6 +12,13 @@ encoder -- the caller supplies the (already L2-normalised) token embeddings and 
   index    nearest centroid by dot product, residual, bucketize, bit-pack            (residual.py:169-204)
   finalize IVF = sorted unique pids per centroid                                    (indexing/utils.py:8-53)
 
+Two forms.  `build_index` holds every embedding on the device at once and returns one chunk.  `ChunkedIndexBuilder` follows the
+reference's chunked run (collection_indexer.py:321-440): plan -> fit the codec on a sample -> compress and write one chunk of
+passages at a time ({i}.codes.pt / {i}.residuals.pt / doclens.{i}.json / {i}.metadata.json, index_saver.py:79-90; chunk i
+belongs to rank i % nranks, collection.py:64-81; with `resume` the chunks already on disk are skipped) -> finalize (offsets,
+IVF over the codes of all chunks).  It never holds more than one chunk of embeddings; fp16 chunks (what encoders emit) go
+through the fused one-pass kernel flmr_compress_f16, fp32 chunks through the two ops below.
+
 Every heavy step runs on the MI355X through the C ABI (`ops`): the nearest-centroid argmax of k-means' assignment step and
 of the final compression (flmr_nearest_centroids: the stage-0 fp16-split MFMA kernel with an argmax epilogue), the residual
 bucketize + bit-pack (flmr_compress_residuals) and the IVF (flmr_build_ivf).  There is no host fallback in this module: the
@@ -19,7 +26,9 @@ embeddings must be on the GPU (tests of the HOST logic -- sampling, the Lloyd lo
 `backend=` an object with the same three functions restated in torch, tests/host_build_backend.py, exactly as they inject an
 encoder).
 """
+import json
 import math
+import os
 
 import torch
 
@@ -39,6 +48,11 @@ class HipBackend:
     def compress_residuals(x, centroids, codes, cutoffs, nbits):
         from . import ops
         return ops.compress_residuals(x, centroids, codes, cutoffs, nbits)
+
+    @staticmethod
+    def compress_f16(x, centroids, cutoffs, nbits):
+        from . import ops
+        return ops.compress_f16(x, centroids, cutoffs, nbits)
 
     @staticmethod
     def build_ivf(codes, doclens, K):
@@ -141,3 +155,203 @@ def build_index(embeddings, doclens, nbits=2, num_partitions=None, kmeans_niters
     cfg.setdefault("kmeans_niters", kmeans_niters)
     return IndexArrays(dim, nbits, cpu(codes), cpu(residuals), cpu(doclens), cpu(ivf), cpu(ivf_lengths), cpu(centroids),
                        cpu(weights), bucket_cutoffs=cpu(cutoffs), avg_residual=avg_residual, config=cfg)
+
+
+def chunks_of_rank(num_chunks, rank, nranks):
+    """The chunks rank `rank` of `nranks` encodes and writes: chunk i belongs to rank i % nranks (collection.py:64-81)."""
+    return [i for i in range(num_chunks) if i % nranks == rank]
+
+
+def _save_atomic(obj, path):
+    tmp = path + ".tmp"
+    if path.endswith(".json"):
+        with open(tmp, "w") as f:
+            json.dump(obj, f, indent=4)
+    else:
+        torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
+class ChunkedIndexBuilder:
+    """Chunk-by-chunk index build into the reference's on-disk layout (collection_indexer.py:321-440, index_saver.py:30-90).
+
+        b = ChunkedIndexBuilder(path, nbits=2, resume=False)
+        b.plan(num_passages, avg_doclen_est)              # plan.json: num_partitions, num_chunks (chunksize passages each)
+        b.fit(sample_embs)                                # k-means + bucket tables -> centroids.pt, buckets.pt, avg_residual.pt
+        for i in chunks_of_rank(b.num_chunks, rank, nranks):
+            b.add_chunk(i, i * b.chunksize, embs_i, doclens_i)   # -> {i}.codes.pt, {i}.residuals.pt, doclens.{i}.json, {i}.metadata.json
+        (barrier: the caller owns the ranks)
+        b.finalize()                                      # embedding offsets, IVF -> ivf.pid.pt, metadata.json
+
+    Only one chunk of embeddings is held at a time; host chunks are moved to the device one at a time.  With `resume`, an
+    existing plan / codec is loaded instead of recomputed and `add_chunk` returns False for a chunk whose code and residual
+    files are already on disk.  `backend` as for `build_index` (tests of the host logic pass a torch one)."""
+
+    def __init__(self, index_path, nbits, resume=False, backend=HipBackend, config=None):
+        assert nbits in (1, 2, 4, 8), nbits
+        self.index_path, self.nbits, self.resume, self.backend = index_path, int(nbits), bool(resume), backend
+        self.config = dict(config or {})
+        self.config.update({"dim": 128, "nbits": self.nbits})
+        self.config.setdefault("kmeans_niters", 4)
+        self.num_partitions = self.num_chunks = self.chunksize = None
+        self.centroids = self.cutoffs = self.weights = self.avg_residual = None
+        os.makedirs(index_path, exist_ok=True)
+
+    def _path(self, name):
+        return os.path.join(self.index_path, name)
+
+    def _dev(self, x):
+        return x.cuda() if self.backend is HipBackend and not x.is_cuda else x
+
+    # ---- plan (collection_indexer.py:75-113) ----
+    def plan(self, num_passages, avg_doclen_est, chunksize=25_000):
+        if self.resume and self._try_load_plan():
+            return False
+        assert num_passages >= 1 and chunksize >= 1
+        num_embeddings_est = num_passages * avg_doclen_est
+        self.num_partitions = num_partitions_for(num_embeddings_est)
+        self.num_chunks = int(math.ceil(num_passages / chunksize))
+        self.chunksize = int(chunksize)
+        self.config["chunksize"] = self.chunksize
+        self._write_plan(num_embeddings_est, avg_doclen_est)
+        return True
+
+    def _write_plan(self, num_embeddings_est, avg_doclen_est):
+        self._plan_est = (num_embeddings_est, avg_doclen_est)
+        _save_atomic({"config": self.config, "num_chunks": self.num_chunks, "num_partitions": self.num_partitions,
+                      "num_embeddings_est": num_embeddings_est, "avg_doclen_est": avg_doclen_est}, self._path("plan.json"))
+
+    def _try_load_plan(self):
+        if not os.path.exists(self._path("plan.json")):
+            return False
+        with open(self._path("plan.json")) as f:
+            plan = json.load(f)
+        self.config.update(plan.get("config", {}))
+        self.num_chunks, self.num_partitions = int(plan["num_chunks"]), int(plan["num_partitions"])
+        self.chunksize = self.config.get("chunksize")
+        self._plan_est = (plan.get("num_embeddings_est"), plan.get("avg_doclen_est"))
+        return True
+
+    # ---- codec (collection_indexer.py:206-308) ----
+    def fit(self, sample_embs, seed=123, heldout_fraction=0.05):
+        """k-means on the sample (held-out split and `kmeans` as in build_index), bucket tables and avg_residual from the
+        held-out residuals; writes centroids.pt / buckets.pt / avg_residual.pt.  Returns False when `resume` loaded them."""
+        assert self.num_partitions is not None, "plan() first"
+        if self.resume and self.try_load_codec():
+            return False
+        sample = self._dev(sample_embs)
+        _require_device(sample, self.backend, "the k-means sample")
+        _require_unit_rows(sample, "fit(sample_embs)")
+        sample = sample.float()
+        n = sample.size(0)
+        K = min(self.num_partitions, n)   # (a sample smaller than the planned partition count: tiny collections)
+        g = torch.Generator(device=sample.device)
+        g.manual_seed(seed)
+        n = min(n, max(K * 40, 1 << 14))   # build_index's sample size
+        sample = sample[torch.randperm(sample.size(0), generator=g, device=sample.device)[:n]]
+        n_held = max(1, min(int(heldout_fraction * n), 50_000))
+        heldout, train = sample[:n_held], sample[n_held:] if n - n_held >= K else sample
+        centroids = kmeans(train, K, int(self.config["kmeans_niters"]), seed, backend=self.backend).half().float()
+        held_codes = self.backend.nearest_centroids(heldout, centroids).long()
+        held_res = heldout - centroids[held_codes]
+        cutoffs, weights = synth.bucket_tables(held_res, self.nbits)
+        self.set_codec(centroids, cutoffs, weights, held_res.abs().mean())
+        return True
+
+    def set_codec(self, centroids, cutoffs, weights, avg_residual):
+        """Use (and write) a given codec: centroids [K, 128] (stored as half), bucket cut-offs [2^nbits - 1] / weights [2^nbits]."""
+        c = torch.as_tensor(centroids)
+        self.centroids = self._dev(c.half().float())
+        self.cutoffs = self._dev(torch.as_tensor(cutoffs).float())
+        self.weights = torch.as_tensor(weights).float()
+        self.avg_residual = torch.as_tensor(avg_residual).float().reshape(()).cpu()
+        assert self.cutoffs.numel() == 2 ** self.nbits - 1 and self.weights.numel() == 2 ** self.nbits
+        if self.num_partitions != c.size(0):   # the codec's centroid count is the index's partition count
+            self.num_partitions = int(c.size(0))
+            if self.num_chunks is not None:
+                self._write_plan(*self._plan_est)
+        _save_atomic(self.centroids.half().cpu(), self._path("centroids.pt"))
+        _save_atomic((self.cutoffs.cpu(), self.weights.cpu()), self._path("buckets.pt"))
+        _save_atomic(self.avg_residual, self._path("avg_residual.pt"))
+
+    def try_load_codec(self):
+        names = ("centroids.pt", "buckets.pt", "avg_residual.pt")
+        if not all(os.path.exists(self._path(x)) for x in names):
+            return False
+        self.centroids = self._dev(torch.load(self._path("centroids.pt"), map_location="cpu").float())
+        cutoffs, weights = torch.load(self._path("buckets.pt"), map_location="cpu")
+        self.cutoffs, self.weights = self._dev(cutoffs.float()), weights.float()
+        self.avg_residual = torch.load(self._path("avg_residual.pt"), map_location="cpu").float()
+        if self.num_partitions is None:
+            self.num_partitions = int(self.centroids.size(0))
+        return True
+
+    # ---- chunks (collection_indexer.py:321-339, index_saver.py:30-90) ----
+    def chunk_exists(self, i):
+        return all(os.path.exists(self._path(f"{i}.{x}.pt")) for x in ("codes", "residuals"))
+
+    def add_chunk(self, i, passage_offset, embs, doclens):
+        """Compress chunk i (passages passage_offset .. + len(doclens)) and write its four files.  Returns False without
+        computing anything when `resume` finds the chunk's codes and residuals on disk."""
+        if self.resume and self.chunk_exists(i):
+            return False
+        assert self.centroids is not None, "fit() / set_codec() first"
+        doclens = [int(x) for x in torch.as_tensor(doclens).reshape(-1).tolist()]
+        n = int(embs.size(0))
+        if sum(doclens) != n:
+            raise ValueError(f"chunk {i}: doclens sum to {sum(doclens)}, the chunk has {n} embeddings")
+        e = self._dev(embs)
+        _require_device(e, self.backend, f"chunk {i}")
+        _require_unit_rows(e, f"add_chunk({i})")
+        if e.dtype == torch.float16:
+            codes, residuals = self.backend.compress_f16(e, self.centroids, self.cutoffs, self.nbits)
+        else:
+            e = e.float()
+            codes = self.backend.nearest_centroids(e, self.centroids)
+            residuals = self.backend.compress_residuals(e, self.centroids, codes, self.cutoffs, self.nbits)
+        # the code file goes last: its presence (with the residuals) marks a complete chunk for `resume`
+        _save_atomic(doclens, self._path(f"doclens.{i}.json"))
+        _save_atomic({"passage_offset": int(passage_offset), "num_passages": len(doclens), "num_embeddings": n},
+                     self._path(f"{i}.metadata.json"))
+        _save_atomic(residuals.to(torch.uint8).cpu(), self._path(f"{i}.residuals.pt"))
+        _save_atomic(codes.to(torch.int32).cpu(), self._path(f"{i}.codes.pt"))
+        return True
+
+    # ---- finalize (collection_indexer.py:341-440) ----
+    def finalize(self):
+        if self.num_chunks is None and not self._try_load_plan():
+            raise FileNotFoundError(f"{self.index_path}: no plan.json (plan() first)")
+        missing = [i for i in range(self.num_chunks) if not (self.chunk_exists(i) and
+                   os.path.exists(self._path(f"doclens.{i}.json")) and os.path.exists(self._path(f"{i}.metadata.json")))]
+        if missing:
+            raise FileNotFoundError(f"{self.index_path}: chunks {missing} of {self.num_chunks} are missing")
+        metas, doclens, codes = [], [], []
+        passage_offset = embedding_offset = 0
+        for i in range(self.num_chunks):
+            with open(self._path(f"{i}.metadata.json")) as f:
+                meta = json.load(f)
+            if int(meta["passage_offset"]) != passage_offset:
+                raise ValueError(f"chunk {i} starts at passage {meta['passage_offset']}, expected {passage_offset} "
+                                 "(chunks must cover the passages contiguously)")
+            with open(self._path(f"doclens.{i}.json")) as f:
+                dl = json.load(f)
+            c = torch.load(self._path(f"{i}.codes.pt"), map_location="cpu")
+            if len(dl) != int(meta["num_passages"]) or c.numel() != int(meta["num_embeddings"]) or sum(dl) != c.numel():
+                raise ValueError(f"chunk {i}: metadata, doclens and codes disagree")
+            meta["embedding_offset"] = embedding_offset
+            metas.append(meta)
+            doclens.extend(dl)
+            codes.append(self._dev(c.to(torch.int32)))
+            passage_offset += len(dl)
+            embedding_offset += c.numel()
+        for i, meta in enumerate(metas):
+            _save_atomic(meta, self._path(f"{i}.metadata.json"))
+        all_codes = torch.cat(codes)   # on the device for the HIP backend
+        del codes
+        ivf, ivf_lengths = self.backend.build_ivf(all_codes, self._dev(torch.tensor(doclens, dtype=torch.int64)),
+                                                  self.num_partitions)
+        _save_atomic((ivf.to(torch.int32).cpu(), ivf_lengths.to(torch.int64).cpu()), self._path("ivf.pid.pt"))
+        _save_atomic({"config": self.config, "num_chunks": self.num_chunks, "num_partitions": self.num_partitions,
+                      "num_embeddings": embedding_offset, "avg_doclen": embedding_offset / max(1, passage_offset)},
+                     self._path("metadata.json"))
+        return self.index_path

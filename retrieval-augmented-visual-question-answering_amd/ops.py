@@ -191,6 +191,32 @@ def compress(embs, centroids, bucket_cutoffs, nbits):
     return codes, compress_residuals(embs, centroids, codes, bucket_cutoffs, nbits)
 
 
+def compress_f16(embs, centroids, bucket_cutoffs, nbits):
+    """ResidualCodec.compress for fp16 token rows in ONE fused pass (flmr_compress_f16) -> (codes int32 [N], residuals uint8
+    [N, 16*nbits]): codes = argmax of the fp32-accumulated fp16 dot product, residual bytes identical to
+    compress_residuals(embs.float(), ...).  embs must be fp16 (no silent rounding of fp32 rows); centroids fp16, or fp32 values
+    that are fp16-representable (what the index stores, residual.py:161)."""
+    lib = _native.load()
+    if torch.as_tensor(embs).dtype != torch.float16:
+        raise TypeError("compress_f16 takes fp16 embeddings (use nearest_centroids + compress_residuals for fp32 rows)")
+    e = _d(embs)
+    c32 = _d(centroids, torch.float32)
+    c = c32.half()
+    if not torch.equal(c.float(), c32):
+        raise ValueError("centroids must be fp16-representable (the index stores them as half): round them with .half() first")
+    cut = _d(bucket_cutoffs, torch.float32)
+    assert e.dim() == 2 and e.size(1) == 128 and c.dim() == 2 and c.size(1) == 128
+    if nbits in (1, 2, 4, 8):
+        assert cut.numel() == 2 ** nbits - 1, "bucket_cutoffs must hold 2^nbits - 1 values"
+    codes = torch.empty(e.size(0), dtype=torch.int32, device="cuda")
+    res = torch.empty((e.size(0), 16 * max(int(nbits), 1)), dtype=torch.uint8, device="cuda")
+    if e.size(0) == 0 and nbits in (1, 2, 4, 8):
+        return codes, res   # (empty tensors may have NULL data pointers, which the C ABI rejects)
+    _native.check(lib.flmr_compress_f16(_p(c), c.size(0), _p(e), e.size(0), _p(cut), int(nbits), _p(codes), _p(res),
+                                        _native.stream_ptr()))
+    return codes, res
+
+
 def build_ivf(codes, doclens, K):
     """(ivf pids int32 [sum unique], ivf_lengths int64 [K]) of an index on the GPU: optimize_ivf (TPC/indexing/utils.py:8-53)
     through flmr_build_ivf -- a stable device radix sort of (code, pid) by code, run flags, compaction."""
