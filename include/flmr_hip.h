@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FLMR_ABI_VERSION 6
+#define FLMR_ABI_VERSION 7
 
 typedef enum flmr_status {
     FLMR_OK = 0,
@@ -331,6 +331,29 @@ int flmr_colbert_score_cross(const float* Q, int32_t nqueries, int32_t nq, const
  * the first 64 columns + the 8 largest of the rest, TPC/modeling/colbert.py:246-261). */
 int flmr_colbert_colmax_padded(const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask, int32_t B,
                                int32_t Ld, int32_t dim, float* out_colmax, flmr_stream_t stream);
+
+/* The padded MaxSim under autograd (colbert_score / colbert_score_reduce, TPC/modeling/colbert.py:235-286, and the in-batch
+ * score tensor of compute_ib_loss_new, :82-113).  Shapes as above; `cross` != 0 selects the cross form, whose rows are
+ * query-major: row r = q * B + b (compute_ib_loss_new's `in_batch_scores[q, p]`, colbert.py:89-92); otherwise rows = B.
+ *
+ * flmr_colbert_maxsim_fwd: out f32[rows] and colmax f32[rows, nq] (each nullable) bit-identical to flmr_colbert_score_padded /
+ *   _cross / flmr_colbert_colmax_padded, plus argmax i32[rows, nq] = the document token whose score is the column maximum.
+ *   Ties go to the LOWEST token, the index torch's max(dim) returns and routes the gradient to (colbert.py:242).  -1 when that
+ *   winner is a padded token (its score was ASSIGNED -9999, colbert.py:240, so no gradient flows through it) or Ld == 0.
+ * flmr_colbert_maxsim_bwd: given that argmax and grad_colmax G f32[rows, nq] = dL/dcolmax (for 'colbert' the score's gradient
+ *   broadcast over the columns; 'flipr' passes what top-k's backward yields), writes
+ *     dQ f32[q_batch, nq, dim]: dQ[qr, i] = sum_r G[r, i] * D[doc(r), argmax[r, i]], the sum over documents for q_batch == 1
+ *       and in the cross form, in ascending document order;
+ *     dD f32[B, Ld, dim]: dD[b, j] = sum of G[r, i] * Q[q(r), i] over the (q, i) of document b whose winner is j, in ascending
+ *       (q, i) order; 0 for padded tokens and tokens that win nothing.
+ *   Either output may be NULL (skipped).  Deterministic: fixed summation orders, no floating-point atomics.
+ * Both enqueue on `stream` and return without synchronising; no workspace.  dim == 128 only (else FLMR_ERR_UNSUPPORTED). */
+int flmr_colbert_maxsim_fwd(const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask, int32_t B,
+                            int32_t Ld, int32_t dim, int32_t cross, float* out, float* colmax, int32_t* argmax,
+                            flmr_stream_t stream);
+int flmr_colbert_maxsim_bwd(const float* Q, int32_t q_batch, int32_t nq, const float* D, int32_t B, int32_t Ld, int32_t dim,
+                            int32_t cross, const int32_t* argmax, const float* grad_colmax, float* dQ, float* dD,
+                            flmr_stream_t stream);
 
 /* Merge per-shard top-k lists after the RCCL all-gather: scores f32[nshards, nqueries, k],
  * pids i32[nshards, nqueries, k] (-1 = empty) -> global top-k per query in descending (score,pid) order. */

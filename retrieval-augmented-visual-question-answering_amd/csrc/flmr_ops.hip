@@ -287,28 +287,64 @@ __global__ __launch_bounds__(256) void score_split_q(const float* Q, int rows, i
     }
 }
 
+// ARGMAX (the autograd forward, flmr_colbert_maxsim_fwd): the same arithmetic, plus the winning token of every column in
+// argmax_out i32 [rows, nq] (-1: padded winner or Ld == 0).  Each lane carries (value, token) through its 16 rows and the
+// half-wave exchange; the LDS column maximum becomes the 64-bit key f2ord(v) << 32 | ~token, whose high word is exactly the
+// fp32 column maximum of the plain instantiation and whose low word makes ties go to the LOWEST token, as torch's max(dim)
+// does under autograd.  That instantiation reads fp32 Q and splits it while staging (the same hi/lo values score_split_q
+// writes), so it needs no workspace and no host synchronisation.
+template <bool ARGMAX>
 __global__ __launch_bounds__(256, 2) void colbert_score_padded_mfma_kernel(const _Float16* __restrict__ q_hi,
-                                                                           const _Float16* __restrict__ q_lo, int q_batch,
+                                                                           const _Float16* __restrict__ q_lo,
+                                                                           const float* __restrict__ Qf, int q_batch,
                                                                            int nq, int nqp, const float* __restrict__ D,
                                                                            const uint8_t* __restrict__ mask, int Ld,
-                                                                           float* out, float* colmax_out) {
+                                                                           float* out, float* colmax_out, int32_t* argmax_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     _Float16* bq = reinterpret_cast<_Float16*>(smem);                                          // [PS_QC][hi|lo][32][PS_BROW]
     unsigned int* colmax = reinterpret_cast<unsigned int*>(bq + PS_QC * 2 * 32 * PS_BROW);     // [nqp] order-preserving fp32 image
+    unsigned long long* colkey = reinterpret_cast<unsigned long long*>(colmax);                 // ARGMAX: [nqp] (value, ~token)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
     // gridDim.y > 1: the CROSS form -- every query (blockIdx.y) against every document, out [gridDim.y, B]
     const size_t ob = (size_t)blockIdx.y * gridDim.x + b;
     const size_t qoff = (gridDim.y > 1 ? (size_t)blockIdx.y : (q_batch == 1 ? 0 : (size_t)b)) * nqp * FLMR_DIM;
-    for (int k = tid; k < nqp; k += 256) colmax[k] = 0u;  // below every real value
+    for (int k = tid; k < nqp; k += 256) {  // below every real value
+        if constexpr (ARGMAX) colkey[k] = 0ull;
+        else colmax[k] = 0u;
+    }
     const int ntiles = (Ld + 31) >> 5;
     for (int qc0 = 0; qc0 < nq; qc0 += 32 * PS_QC) {
         const int ntq = ((nq - qc0 < 32 * PS_QC ? nq - qc0 : 32 * PS_QC) + 31) >> 5;
         __syncthreads();
-        for (int e = tid; e < ntq * 1024; e += 256) {
-            const int piece = e & 15, row = (e >> 4) & 31, hl = (e >> 9) & 1, qt = e >> 10;
-            const _Float16* src = (hl ? q_lo : q_hi) + qoff + (size_t)(qc0 + qt * 32 + row) * FLMR_DIM + piece * 8;
-            *reinterpret_cast<ph8*>(bq + ((qt * 2 + hl) * 32 + row) * PS_BROW + piece * 8) = *reinterpret_cast<const ph8*>(src);
+        if constexpr (ARGMAX) {   // fp32 Q [rows, nq, 128] split on the fly; rows >= nq stage as zero (score_split_q's rule)
+            const size_t qrow0 = qoff / ((size_t)nqp * FLMR_DIM) * nq;
+            for (int e = tid; e < ntq * 512; e += 256) {
+                const int piece = e & 15, row = (e >> 4) & 31, qt = e >> 9, r = qc0 + qt * 32 + row;
+                ph8 hi8, lo8;
+                if (r < nq) {
+                    const float4* src = reinterpret_cast<const float4*>(Qf + (qrow0 + r) * FLMR_DIM + piece * 8);
+                    const float4 x = src[0], y = src[1];
+                    const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+#pragma unroll
+                    for (int k = 0; k < 8; k++) {
+                        const _Float16 hi = (_Float16)v[k];
+                        hi8[k] = hi;
+                        lo8[k] = (_Float16)((v[k] - (float)hi) * 2048.0f);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 8; k++) { hi8[k] = (_Float16)0.0f; lo8[k] = (_Float16)0.0f; }
+                }
+                *reinterpret_cast<ph8*>(bq + ((qt * 2 + 0) * 32 + row) * PS_BROW + piece * 8) = hi8;
+                *reinterpret_cast<ph8*>(bq + ((qt * 2 + 1) * 32 + row) * PS_BROW + piece * 8) = lo8;
+            }
+        } else {
+            for (int e = tid; e < ntq * 1024; e += 256) {
+                const int piece = e & 15, row = (e >> 4) & 31, hl = (e >> 9) & 1, qt = e >> 10;
+                const _Float16* src = (hl ? q_lo : q_hi) + qoff + (size_t)(qc0 + qt * 32 + row) * FLMR_DIM + piece * 8;
+                *reinterpret_cast<ph8*>(bq + ((qt * 2 + hl) * 32 + row) * PS_BROW + piece * 8) = *reinterpret_cast<const ph8*>(src);
+            }
         }
         __syncthreads();
         for (int t = wave; t < ntiles; t += 4) {
@@ -349,24 +385,46 @@ __global__ __launch_bounds__(256, 2) void colbert_score_padded_mfma_kernel(const
                     accm = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh, accm, 0, 0, 0);
                 }
                 float mx = FLMR_NEG_INF;
+                int arg = 0x7fffffff;   // ARGMAX: the lowest row holding mx (rows ascend with r for a fixed h)
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                     const float v = ((okbits >> r) & 1u) ? fmaf(accl[r] + accm[r], 1.0f / 2048.0f, acch[r]) : -9999.0f;  // colbert.py:240
-                    if (row < Ld) mx = fmaxf(mx, v);
+                    if constexpr (ARGMAX) {
+                        if (row < Ld && v > mx) { mx = v; arg = row; }
+                    } else {
+                        if (row < Ld) mx = fmaxf(mx, v);
+                    }
                 }
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
                 const int col = qc0 + qt * 32 + i;
-                if (h == 0 && col < nq && mx > FLMR_NEG_INF) atomicMax(&colmax[col], flmr_f2ord(mx));
+                if constexpr (ARGMAX) {
+                    const float omx = __shfl_xor(mx, 32, 64);
+                    const int oarg = __shfl_xor(arg, 32, 64);
+                    if (omx > mx || (omx == mx && oarg < arg)) { mx = omx; arg = oarg; }
+                    if (h == 0 && col < nq && mx > FLMR_NEG_INF)
+                        atomicMax(&colkey[col], ((unsigned long long)flmr_f2ord(mx) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)arg));
+                } else {
+                    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                    if (h == 0 && col < nq && mx > FLMR_NEG_INF) atomicMax(&colmax[col], flmr_f2ord(mx));
+                }
             }
         }
     }
     __syncthreads();
+    auto cmax = [&](int k) -> float {
+        if constexpr (ARGMAX) return (Ld > 0) ? flmr_ord2f((unsigned int)(colkey[k] >> 32)) : FLMR_NEG_INF;
+        else return (Ld > 0) ? flmr_ord2f(colmax[k]) : FLMR_NEG_INF;
+    };
+    if constexpr (ARGMAX)
+        for (int k = tid; k < nq; k += 256) {
+            const int tok = (Ld > 0) ? (int)(0xFFFFFFFFu - (uint32_t)colkey[k]) : -1;
+            argmax_out[ob * nq + k] = (tok >= 0 && mask[(size_t)b * Ld + tok]) ? tok : -1;
+        }
     if (colmax_out)
-        for (int k = tid; k < nq; k += 256) colmax_out[ob * nq + k] = (Ld > 0) ? flmr_ord2f(colmax[k]) : FLMR_NEG_INF;
+        for (int k = tid; k < nq; k += 256) colmax_out[ob * nq + k] = cmax(k);
     if (tid == 0 && out) {
         float sc = 0.0f;
-        for (int k = 0; k < nq; k++) sc += (Ld > 0) ? flmr_ord2f(colmax[k]) : FLMR_NEG_INF;
+        for (int k = 0; k < nq; k++) sc += cmax(k);
         out[ob] = sc;
     }
 }
@@ -390,9 +448,10 @@ static int score_padded(const float* Q, int32_t q_batch, int32_t nq, const float
         RUN(sc.alloc(&ql, (size_t)q_batch * nqp * FLMR_DIM));
         hipLaunchKernelGGL(score_split_q, dim3(1024), dim3(256), 0, st, Q, q_batch, nq, nqp, qh, ql);
         const size_t lds = (size_t)PS_QC * 2 * 32 * PS_BROW * sizeof(_Float16) + (size_t)nqp * sizeof(unsigned int);
-        FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_padded_mfma_kernel),
+        FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_padded_mfma_kernel<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(colbert_score_padded_mfma_kernel, grid, dim3(256), lds, st, qh, ql, q_batch, nq, nqp, D, mask, Ld, out, colmax_out);
+        hipLaunchKernelGGL(colbert_score_padded_mfma_kernel<false>, grid, dim3(256), lds, st, qh, ql, nullptr, q_batch, nq, nqp, D,
+                           mask, Ld, out, colmax_out, nullptr);
         FLMR_LAUNCH_CHECK();
         FLMR_HIP(hipStreamSynchronize(st));  // the split buffers are released on return
         return FLMR_OK;
@@ -422,6 +481,30 @@ extern "C" int flmr_colbert_colmax_padded(const float* Q, int32_t q_batch, int32
                                           int32_t B, int32_t Ld, int32_t dim, float* out_colmax, flmr_stream_t stream) {
     if (!out_colmax) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     return score_padded(Q, q_batch, nq, D, mask, B, Ld, dim, nullptr, out_colmax, stream);
+}
+
+// the autograd forward (include/flmr_hip.h): the ARGMAX instantiation of the MFMA kernel -- the same per-column maxima and
+// sums as the three entry points above, bit for bit, plus the winning token of each column.  No workspace, no host sync.
+extern "C" int flmr_colbert_maxsim_fwd(const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask,
+                                       int32_t B, int32_t Ld, int32_t dim, int32_t cross, float* out, float* colmax,
+                                       int32_t* argmax, flmr_stream_t stream) {
+    if (!Q || !D || !mask || !argmax) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
+    if (!cross && q_batch != 1 && q_batch != B) FLMR_FAIL(FLMR_ERR_INVALID, "q_batch must be 1 or B");
+    if (cross && (q_batch < 1 || q_batch > 65535)) FLMR_FAIL(FLMR_ERR_INVALID, "cross scoring takes 1..65535 queries per call");
+    if (nq < 1 || B < 0 || Ld < 0) FLMR_FAIL(FLMR_ERR_INVALID, "bad sizes");
+    if (dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dim=%d (this build: %d)", dim, FLMR_DIM);
+    if ((size_t)nq * 8 > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
+    if (B == 0) return FLMR_OK;
+    const dim3 grid((unsigned)B, cross ? (unsigned)q_batch : 1u);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int nqp = (int)flmr_round_up(nq, 32);
+    const size_t lds = (size_t)PS_QC * 2 * 32 * PS_BROW * sizeof(_Float16) + (size_t)nqp * sizeof(unsigned long long);
+    FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_padded_mfma_kernel<true>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(colbert_score_padded_mfma_kernel<true>, grid, dim3(256), lds, st, nullptr, nullptr, Q, q_batch, nq, nqp,
+                       D, mask, Ld, out, colmax, argmax);
+    FLMR_LAUNCH_CHECK();
+    return FLMR_OK;
 }
 
 // ---- merge of per-shard top-k lists (after the RCCL all-gather) -----------------------------------------

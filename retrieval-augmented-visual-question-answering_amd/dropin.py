@@ -26,6 +26,14 @@ front-ends of the C ABI (same signatures; INTEGRATION.md level 2).  `uninstall()
 so `ColBERT.score` (TPC/modeling/colbert.py:217-224) -- what the FLMR model classes inherit and what the exhaustive
 search (`src/executors/FLMR_executor.py:833`) and the RAG re-scoring (`src/models/rag/rag_model_blip.py:435`) call --
 reaches the MI355X kernel in a drop-in run, while training (in-batch negatives under autograd) is untouched.
+
+`scoring="autograd"` (opt-in) routes the grad-requiring `colbert_score` calls of the kernel's shapes to the differentiable
+HIP path as well (`scoring.colbert_score_differentiable`), and rebinds
+
+    colbert.modeling.colbert.ColBERT.compute_ib_loss_new -> `scoring.in_batch_negative_loss` with the module's own
+                                                            `colbert_config` and `loss_fn` (colbert.py:82-113)
+
+so the re-scoring inside the RAG model and the in-batch loss of retriever training run on the MI355X too.
 """
 import importlib
 import warnings
@@ -69,7 +77,7 @@ def _import_reference(package):
             "it does not replace it.") from e
 
 
-def make_colbert_score_dispatch(reference_colbert_score):
+def make_colbert_score_dispatch(reference_colbert_score, autograd=False):
     """The function bound over the reference's `colbert_score` (TPC/modeling/colbert.py:268-286).
 
     HIP path (flmr_colbert_score_padded: fp16-split MFMA, -9999 padding, no clamp, fp32 accumulation) when the call is
@@ -81,6 +89,9 @@ def make_colbert_score_dispatch(reference_colbert_score):
     device is visible in the process (a CPU-only validation run of the reference) the call is not intercepted at all -- it
     goes to the reference's expression, with one RuntimeWarning.  With a device visible there is no host fallback: a missing
     or broken libflmr_hip.so raises FlmrNativeError.  (The search path -- Searcher / IndexScorer -- never passes through.)
+
+    With `autograd=True` (install(scoring="autograd")) grad-requiring calls of those shapes run the differentiable HIP path
+    (scoring.colbert_score_differentiable) instead of the reference's expression.
 
     Arithmetic: as in the reference Q is first rounded to D_padded's dtype (colbert.py:280: `Q.to(dtype=D_padded.dtype)`);
     the products of those values are then exact and accumulated in fp32, and only the final per-passage score is rounded to
@@ -102,7 +113,7 @@ def make_colbert_score_dispatch(reference_colbert_score):
         shape_ok = (torch.is_tensor(Q) and torch.is_tensor(D_padded) and Q.dim() == 3 and D_padded.dim() == 3
                     and Q.size(0) in (1, D_padded.size(0)) and Q.size(-1) == D_padded.size(-1)
                     and Q.is_floating_point() and D_padded.is_floating_point() and D_padded.size(0) > 0 and D_padded.size(1) > 0)
-        if not (forward_only and shape_ok and interaction in ("colbert", "flipr")):
+        if not ((forward_only or autograd) and shape_ok and interaction in ("colbert", "flipr")):
             return reference(Q, D_padded, D_mask, config, use_gpu)
         if not _native.device_visible():
             if not state["warned"]:
@@ -110,13 +121,17 @@ def make_colbert_score_dispatch(reference_colbert_score):
                 warnings.warn("ravqa_amd: no HIP device is visible in this process -- colbert_score calls are left to the "
                               "reference's torch expression (the HIP scorer takes them when a device is present)", RuntimeWarning)
             return reference(Q, D_padded, D_mask, config, use_gpu)
+        dev = torch.device("cuda") if use_gpu else D_padded.device
+        if not forward_only:   # (autograd=True) the gradient flows through the cast and the device moves as in the reference
+            from . import scoring
+            out = scoring.colbert_score_differentiable(Q.to(dtype=D_padded.dtype), D_padded, D_mask, config)
+            return out.to(device=dev, dtype=D_padded.dtype)
         Qr = Q.detach().to(dtype=D_padded.dtype)                                   # colbert.py:280
         if interaction == "flipr":   # colbert.py:246-261: the column maxima from the HIP kernel, their top-k sums in scoring.reduce_colmax
             from . import scoring
             out = scoring.reduce_colmax(ops.colbert_colmax_padded(Qr, D_padded.detach(), D_mask), config)
         else:
             out = ops.colbert_score_padded(Qr, D_padded.detach(), D_mask)          # f32 on the device
-        dev = torch.device("cuda") if use_gpu else D_padded.device
         return out.to(device=dev, dtype=D_padded.dtype)
 
     colbert_score.__doc__ = (reference_colbert_score.__doc__ or "") + "\n    [ravqa_amd: forward-only calls run flmr_colbert_score_padded on the MI355X]"
@@ -125,14 +140,43 @@ def make_colbert_score_dispatch(reference_colbert_score):
     return colbert_score
 
 
-def _install_scoring(package):
+def make_ib_loss(reference_compute_ib_loss_new):
+    """The method bound over ColBERT.compute_ib_loss_new (colbert.py:82-113) by install(scoring="autograd"):
+    scoring.in_batch_negative_loss with `self.colbert_config` and `self.loss_fn`.  Shapes the kernel does not take, an
+    interaction other than 'colbert' / 'flipr', or no visible HIP device go to the reference's method."""
+    import torch
+
+    def compute_ib_loss_new(self, Q, D, D_mask):
+        from . import _native, scoring
+        config = getattr(self, "colbert_config", None)
+        interaction = getattr(config, "interaction", "colbert") if config is not None else "colbert"
+        shape_ok = (torch.is_tensor(Q) and torch.is_tensor(D) and Q.dim() == 3 and D.dim() == 3 and Q.size(-1) == D.size(-1)
+                    and Q.is_floating_point() and D.is_floating_point() and Q.size(0) > 0 and D.size(0) > 0 and D.size(1) > 0
+                    and D.size(0) % Q.size(0) == 0)
+        if not (shape_ok and interaction in ("colbert", "flipr")) or not _native.device_visible():
+            return reference_compute_ib_loss_new(self, Q, D, D_mask)
+        return scoring.in_batch_negative_loss(Q, D, D_mask, config, loss_fn=getattr(self, "loss_fn", None))
+
+    compute_ib_loss_new.__doc__ = (reference_compute_ib_loss_new.__doc__ or "") + "\n    [ravqa_amd: HIP MaxSim forward + backward]"
+    compute_ib_loss_new.__wrapped__ = reference_compute_ib_loss_new
+    compute_ib_loss_new.__ravqa_amd__ = True
+    return compute_ib_loss_new
+
+
+def _install_scoring(package, autograd=False):
     """Rebind `colbert_score` in colbert.modeling.colbert (ColBERT.score resolves it there at call time) and in every
-    module that imported the name before install() (index_storage.py:12 does)."""
+    module that imported the name before install() (index_storage.py:12 does); with `autograd` also
+    ColBERT.compute_ib_loss_new."""
     mc = _import_reference(package + ".modeling.colbert")
+    if autograd:
+        cls = getattr(mc, "ColBERT", None)
+        ref_loss = cls.__dict__.get("compute_ib_loss_new") if cls is not None else None
+        if ref_loss is not None and not getattr(ref_loss, "__ravqa_amd__", False):
+            _bind(cls, "compute_ib_loss_new", make_ib_loss(ref_loss))
     reference_fn = getattr(mc, "colbert_score", None)
     if reference_fn is None or getattr(reference_fn, "__ravqa_amd__", False):
         return
-    dispatch = make_colbert_score_dispatch(reference_fn)
+    dispatch = make_colbert_score_dispatch(reference_fn, autograd=autograd)
     _bind(mc, "colbert_score", dispatch)
     for mod in list(sys.modules.values()):
         d = getattr(mod, "__dict__", None)
@@ -146,12 +190,15 @@ def install(level="searcher", package="colbert", require_device=False, scoring=T
     """Patch the reference's `colbert` package (see module docstring).  Returns the installed Searcher class
     (level "searcher") or the list of patched op names (level "ops").  Idempotent.  `require_device=True` also
     checks that libflmr_hip.so loads and a HIP device is visible (the search path has no CPU fallback).
-    `scoring=True` also routes forward-only `colbert_score` / `ColBERT.score` calls to the HIP padded scorer."""
+    `scoring=True` also routes forward-only `colbert_score` / `ColBERT.score` calls to the HIP padded scorer;
+    `scoring="autograd"` routes grad-requiring ones (and ColBERT.compute_ib_loss_new) to the differentiable HIP path too."""
     global _installed
     if _installed is not None:
         return _installed
     if level not in ("searcher", "ops"):
         raise ValueError(f"level must be 'searcher' or 'ops', got {level!r}")
+    if scoring not in (True, False, None, "autograd"):
+        raise ValueError(f"scoring must be True, False or 'autograd', got {scoring!r}")
     from . import _native
     if require_device:
         _native.load(require_device=True)
@@ -159,7 +206,7 @@ def install(level="searcher", package="colbert", require_device=False, scoring=T
     if getattr(ref, "__ravqa_amd__", False):
         raise ImportError(f"`{package}` resolves to a ravqa_amd shim, not to the reference package")
     if scoring:
-        _install_scoring(package)
+        _install_scoring(package, autograd=(scoring == "autograd"))
 
     if level == "ops":
         from . import ops

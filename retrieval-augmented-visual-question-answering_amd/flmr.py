@@ -14,6 +14,10 @@ the text tokens, the L2 normalisation, `keep_dims` handling, and the MaxSim scor
 (`flmr_colbert_score_padded`) -- forward only: `score` raises under autograd instead of silently computing without a graph.
 `forward` returns the scores of every query against its `nway` passages; the in-batch-negative LOSS of training
 (`compute_ib_loss_new`, colbert.py:82-128) is not part of the retrieval path and raises if requested.
+
+`differentiable=True` opts into the HIP MaxSim under autograd (scoring.colbert_score_differentiable): `score` then carries
+gradients back to Q and D, and `forward` under grad with `use_ib_negatives` returns `(scores, ib_loss)` as colbert.py:75-78
+does, the loss from scoring.in_batch_negative_loss.
 """
 import string
 
@@ -24,8 +28,10 @@ from . import scoring
 
 class FLMRModelForRetrieval:
     def __init__(self, text_encoder, doc_encoder=None, vision_projection=None, colbert_config=None, skiplist=None,
-                 mask_punctuation_ids=None, dim=128, device=None):
+                 mask_punctuation_ids=None, dim=128, device=None, differentiable=False):
         self.text_encoder = text_encoder
+        self.differentiable = bool(differentiable)
+        self.loss_fn = torch.nn.CrossEntropyLoss()   # colbert.py:42
         self.doc_encoder = doc_encoder or text_encoder
         self.vision_projection = vision_projection
         self.colbert_config = colbert_config
@@ -77,6 +83,8 @@ class FLMRModelForRetrieval:
             # colbert.py:220-222: the squared-distance variant is a plain torch expression upstream (no mask, no kernel): kept as it is
             assert getattr(self.colbert_config, "interaction", "colbert") == "colbert"
             return (-1.0 * ((Q.unsqueeze(2) - D_padded.unsqueeze(1)) ** 2).sum(-1)).max(-1).values.sum(-1)
+        if self.differentiable:
+            return scoring.colbert_score_differentiable(Q, D_padded, D_mask, config=self.colbert_config)
         return scoring.colbert_score(Q, D_padded, D_mask, config=self.colbert_config)
 
     # ---- colbert.py:64-80 ---------------------------------------------------------------------------------------------
@@ -87,6 +95,8 @@ class FLMRModelForRetrieval:
         Q_duplicated = Q.repeat_interleave(nway, dim=0).contiguous()
         scores = self.score(Q_duplicated, D, D_mask)
         if self.colbert_config is not None and getattr(self.colbert_config, "use_ib_negatives", False) and torch.is_grad_enabled():
+            if self.differentiable:   # colbert.py:75-78
+                return scores, scoring.in_batch_negative_loss(Q, D, D_mask, self.colbert_config, loss_fn=self.loss_fn)
             raise NotImplementedError("the in-batch-negative loss (colbert.py:82-128) belongs to training; call forward under "
                                       "torch.no_grad() for the retrieval scores")
         return scores

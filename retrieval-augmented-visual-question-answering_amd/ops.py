@@ -121,6 +121,49 @@ def colbert_colmax_padded(Q, D_padded, D_mask):
     return out
 
 
+def colbert_maxsim_fwd(Q, D_padded, D_mask, cross=False, want_out=True, want_colmax=False):
+    """The autograd forward (flmr_colbert_maxsim_fwd): fp32 CUDA Q [q_batch, Nq, 128], D [B, Ld, 128], mask [B, Ld(,1)] ->
+    (out f32 [rows] | None, colmax f32 [rows, Nq] | None, argmax i32 [rows, Nq]); rows = B, or q_batch * B query-major when
+    `cross` (returned there as [q_batch, B] / [q_batch, B, Nq]).  argmax = the winning token, lowest on ties, -1 where the
+    winner is padded.  out / colmax are bit-identical to colbert_score_padded / colbert_score_cross / colbert_colmax_padded.
+    Enqueued on the current stream, no synchronisation."""
+    lib = _native.load()
+    Qd, Dd = _d(Q, torch.float32), _d(D_padded, torch.float32)
+    B, Ld, dim = Dd.shape
+    nQ, nq = Qd.size(0), Qd.size(1)
+    md = _d(torch.as_tensor(D_mask).reshape(B, Ld), torch.bool).view(torch.uint8)
+    lead = (nQ, B) if cross else (B,)
+    out = torch.empty(lead, dtype=torch.float32, device="cuda") if want_out else None
+    colmax = torch.empty(lead + (nq,), dtype=torch.float32, device="cuda") if want_colmax else None
+    argmax = torch.empty(lead + (nq,), dtype=torch.int32, device="cuda")
+    if B == 0:
+        return out, colmax, argmax   # (empty tensors may have NULL data pointers, which the C ABI rejects)
+    _native.check(lib.flmr_colbert_maxsim_fwd(_p(Qd), nQ, nq, _p(Dd), _p(md), B, Ld, dim, int(bool(cross)), _p(out), _p(colmax),
+                                              _p(argmax), _native.stream_ptr()))
+    return out, colmax, argmax
+
+
+def colbert_maxsim_bwd(Q, D_padded, argmax, grad_colmax, cross=False, need_dQ=True, need_dD=True):
+    """The autograd backward (flmr_colbert_maxsim_bwd): from the forward's argmax and G = dL/dcolmax (shaped like argmax) ->
+    (dQ f32 [q_batch, Nq, 128] | None, dD f32 [B, Ld, 128] | None).  Deterministic; enqueued on the current stream."""
+    lib = _native.load()
+    Qd, Dd = _d(Q, torch.float32), _d(D_padded, torch.float32)
+    B, Ld, dim = Dd.shape
+    nQ, nq = Qd.size(0), Qd.size(1)
+    am, G = _d(argmax, torch.int32), _d(grad_colmax, torch.float32)
+    rows = nQ * B if cross else B
+    assert am.numel() == rows * nq and G.numel() == rows * nq, (tuple(am.shape), tuple(G.shape), rows, nq)
+    dQ = torch.empty_like(Qd) if need_dQ else None
+    dD = torch.empty_like(Dd) if need_dD else None
+    if B == 0:
+        if dQ is not None:
+            dQ.zero_()
+        return dQ, dD
+    _native.check(lib.flmr_colbert_maxsim_bwd(_p(Qd), nQ, nq, _p(Dd), B, Ld, dim, int(bool(cross)), _p(am), _p(G), _p(dQ), _p(dD),
+                                              _native.stream_ptr()))
+    return dQ, dD
+
+
 def merge_topk(scores, pids):
     """scores f32 / pids i32 [nshards, nqueries, k] (CUDA) -> merged (scores, pids, counts) [nqueries, k]."""
     lib = _native.load()

@@ -2,8 +2,12 @@
 `colbert_score_reduce` and `ColBERT.segmented_maxsim` (TPC/modeling/colbert.py:235-311) and of the inherited
 `score(Q, D_padded, D_mask)` of the FLMR model classes (src/models/retriever/FLMR.py; TPC/modeling/colbert.py:217-224).
 
-Forward only.  When autograd needs the score (training, in-batch negatives) the caller must keep using its torch
-expression: these functions raise if an input requires grad instead of silently computing without a graph.
+`colbert_score` and the other search-side functions are forward only: they raise if an input requires grad instead of
+silently computing without a graph.  The score under autograd -- RA-VQA's re-scoring inside the RAG model
+(src/models/rag/rag_model_blip.py:430-435) and the in-batch-negative loss of retriever training (`compute_ib_loss_new`,
+colbert.py:82-113) -- goes through `colbert_score_differentiable`, `colbert_score_cross_differentiable` and
+`in_batch_negative_loss`: the HIP forward records the winning token of every column and the HIP backward gathers the
+gradients from it (flmr_colbert_maxsim_fwd / _bwd), so the [B, Ld, Nq] score tensor is never materialised.
 """
 import torch
 
@@ -50,6 +54,70 @@ def colbert_score(Q, D_padded, D_mask, config=None, use_gpu=False):
     if _interaction(config) == "flipr":
         return reduce_colmax(ops.colbert_colmax_padded(Q, D_padded, D_mask), config)
     return ops.colbert_score_padded(Q, D_padded, D_mask)
+
+
+_device = "cuda"   # where the kernels run (the CPU plumbing tests point this at "cpu" with stand-in ops)
+
+
+class _MaxSim(torch.autograd.Function):
+    """Padded MaxSim with the gradient torch's autograd gives colbert_score_reduce (colbert.py:235-263): each column's
+    gradient goes to its winning token, the lowest one on ties, and nowhere when that token is padded.  Returns the kernel's
+    per-row sum (`colbert`, [rows]) or the per-column maxima ([rows, Nq]); rows are [nQ, B] in the cross form."""
+
+    @staticmethod
+    def forward(ctx, Q, D_padded, D_mask, cross, want_colmax):
+        out, colmax, argmax = ops.colbert_maxsim_fwd(Q.detach().float(), D_padded.detach().float(), D_mask, cross=cross,
+                                                     want_out=not want_colmax, want_colmax=want_colmax)
+        ctx.save_for_backward(Q, D_padded, argmax)
+        ctx.cross, ctx.want_colmax = cross, want_colmax
+        return colmax if want_colmax else out
+
+    @staticmethod
+    def backward(ctx, grad):
+        Q, D_padded, argmax = ctx.saved_tensors
+        need_dQ, need_dD = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_dQ or need_dD):
+            return None, None, None, None, None
+        G = grad.float() if ctx.want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)
+        dQ, dD = ops.colbert_maxsim_bwd(Q.detach().float(), D_padded.detach().float(), argmax, G.contiguous(), cross=ctx.cross,
+                                        need_dQ=need_dQ, need_dD=need_dD)
+        return (dQ.to(Q.dtype) if need_dQ else None, dD.to(D_padded.dtype) if need_dD else None, None, None, None)
+
+
+def _maxsim(Q, D_padded, D_mask, config, cross):
+    if Q.dim() != 3 or D_padded.dim() != 3 or Q.size(-1) != D_padded.size(-1):
+        raise ValueError(f"Q {tuple(Q.shape)} / D {tuple(D_padded.shape)}: expected [n, Nq, d] and [B, Ld, d]")
+    if not cross and Q.size(0) not in (1, D_padded.size(0)):
+        raise ValueError(f"Q.size(0) = {Q.size(0)} must be 1 or B = {D_padded.size(0)}")   # colbert.py:278
+    Q, D_padded = Q.to(_device), D_padded.to(_device)
+    if _interaction(config) == "flipr":
+        return reduce_colmax(_MaxSim.apply(Q, D_padded, D_mask, cross, True).flatten(0, -2), config).reshape(
+            (Q.size(0), D_padded.size(0)) if cross else (D_padded.size(0),))
+    return _MaxSim.apply(Q, D_padded, D_mask, cross, False)
+
+
+def colbert_score_differentiable(Q, D_padded, D_mask, config=None):
+    """colbert_score (colbert.py:268-286) under autograd: Q [1|B, Nq, 128], D [B, Ld, 128] -> f32 [B] on the device, with
+    dQ / dD equal to what torch's autograd gives the reference expression.  fp16 / bf16 inputs are widened exactly to fp32;
+    gradients come back in each input's dtype.  'colbert' values are bit-identical to ops.colbert_score_padded; 'flipr'
+    reduces the differentiable column maxima with reduce_colmax."""
+    return _maxsim(Q, D_padded, D_mask, config, cross=False)
+
+
+def colbert_score_cross_differentiable(Q, D_padded, D_mask, config=None):
+    """Every query against every document under autograd: Q [nQ, Nq, 128], D [B, Ld, 128] -> f32 [nQ, B] -- the
+    `in_batch_scores` of compute_ib_loss_new (colbert.py:86-92, query-major), values bit-identical to ops.colbert_score_cross."""
+    return _maxsim(Q, D_padded, D_mask, config, cross=True)
+
+
+def in_batch_negative_loss(Q, D, D_mask, config=None, loss_fn=None):
+    """compute_ib_loss_new (colbert.py:82-113): Q [nQ, Nq, 128], D [nQ * nway, Ld, 128] -> the cross-entropy of every query's
+    scores against all nQ * nway documents, the label of query q being its first passage, column q * nway.  `loss_fn` defaults
+    to torch.nn.CrossEntropyLoss() (colbert.py:42)."""
+    scores = colbert_score_cross_differentiable(Q, D, D_mask, config)
+    nway = D.size(0) // Q.size(0)
+    labels = torch.arange(Q.size(0), device=scores.device) * nway
+    return (loss_fn or torch.nn.CrossEntropyLoss())(scores, labels)
 
 
 def colbert_score_packed(Q, D_packed, D_lengths, config=None):
