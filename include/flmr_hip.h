@@ -48,21 +48,27 @@ const char* flmr_last_error(void);
 int flmr_device_count(int* count);
 /* Kernel-variant switches for A/B runs and cross-check tests (FLMR_S0_IMPL, FLMR_FULL_TABLE, FLMR_CAND_IMPL,
  * FLMR_S1_NO_HITMAP, FLMR_S1_IMPL, FLMR_S2_IMPL, FLMR_S0_STAGED, FLMR_S3_NO_MULTIQ, FLMR_S3_IMPL, FLMR_SCORE_IMPL).  The
- * environment variables of the same names are read ONCE per process, on first use of the library; afterwards the table
- * changes only through this call (value NULL or "" clears a switch).  Op-level entry points read the table when they are
- * called; a searcher snapshots it at flmr_searcher_create and keeps that snapshot.  Nothing on the per-batch launch path
- * reads the environment.  (The reference has no counterpart: its extensions have one implementation each.)
+ * environment variables of the same names (FLMR_POISON, FLMR_ROW_CAP too) are read and parsed ONCE per process, on first use
+ * of the library; afterwards the switches change only through this call (value NULL or "" clears a switch).  Each switch
+ * takes exactly the values named here (FLMR_S0_IMPL = qs1 | f16 | f16rs | f32 | mfma | valu; FLMR_S1_IMPL = scan | slots | image;
+ * FLMR_S2_IMPL = xcda | xcd | walk | lds, plus regs | ldsb in FLMR_EXPERIMENTAL_VARIANTS builds; FLMR_S3_IMPL = qs | lean | cw |
+ * cwregs | dma | regs | f32; FLMR_CAND_IMPL = atomic; FLMR_SCORE_IMPL = valu; FLMR_ROW_CAP = an integer; the others are set by
+ * any value): any other value returns FLMR_ERR_INVALID with the accepted values in flmr_last_error(), and such a value in the
+ * environment makes flmr_index_open, flmr_searcher_create and the op-level calls that consult switches fail the same way.
+ * Op-level entry points read the switches when they are called; a searcher snapshots them at flmr_searcher_create and plans
+ * every batch from that snapshot.  Nothing on the per-batch launch path reads the environment.  (The reference has no
+ * counterpart: its extensions have one implementation each.)
  * Values with a measured use: FLMR_S2_IMPL = xcd | lds | ldsb | walk | regs (stage 2: one L2-resident table slice per XCD --
  * the default for whole batches when the fp16 centroid table exceeds an L2 -- / row gather with 4-wave or 16-wave blocks /
  * dense table walk / register gather); FLMR_S3_IMPL = lean | cw | cwregs | regs | dma | f32 | qs (fused MaxSim.  Nq <= 32: lean, the
  * default = the centroid + weight arithmetic on planned tiles; cw / cwregs = the same arithmetic walking the passages, rows by
  * LDS-DMA / register gathers; regs / dma = decompress-normalise-split; f32 = fp32-MFMA kernel.  Longer queries: qs, the
- * query-stationary kernel, the default from 288 rows; any other value = the chunked kernel); FLMR_S1_IMPL = scan | slots
+ * query-stationary kernel, the default from 288 rows; any other value = the chunked kernel); FLMR_S1_IMPL = scan | slots | image
  * (stage 1: the code-scanning kernel for every query / the slot form of the list-scatter kernel for every query; default: its
  * queue form first, the slot form for the queries that one hands over, and beyond the list-scatter forms' limits -- more than 1024
  * surviving centroids, lists far longer than the probed cells' -- the dense forms of flmr_stage1_dense.hip: fp16 images of the
  * query's score rows in LDS, upper-bound keys for every candidate, the band around the cut rescored exactly; the exact form alone
- * when the rows do not fit).
+ * when the rows do not fit; image: the queries beyond the images go to the code scan).
  * Variants of one arithmetic are bit-identical to each other, the arithmetics agree to fp32 roundoff (tests/test_hip_parity.py).
  * One switch is a capacity, not a variant: FLMR_ROW_CAP = score rows a searcher keeps per query (64 .. 65535, default 16384,
  * never more than K).  The default path stores the centroid scores of a query only for the centroids that pass

@@ -10,7 +10,13 @@
 
 thread_local char flmr_err_buf[512] = {0};
 static flmr_options g_opts;
-const flmr_options& flmr_opts() { return g_opts; }
+static s3_sw s3_value(const char* v) {   // the FLMR_S3_IMPL names
+    const char* names[] = {"", "qs", "lean", "cw", "cwregs", "dma", "regs", "f32"};
+    for (int i = 1; i < 8; i++)
+        if (strcmp(v, names[i]) == 0) return (s3_sw)i;
+    printf("unknown form %s (qs lean cw cwregs dma regs f32)\n", v);
+    exit(1);
+}
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
 int main(int argc, char** argv) {
@@ -18,7 +24,7 @@ int main(int argc, char** argv) {
     const int NQR = getenv("S3P_NQ") ? atoi(getenv("S3P_NQ")) : 32;          // S3P_NQ: query rows (> 32: the long-query kernels)
     const int NQ = getenv("S3P_B") ? atoi(getenv("S3P_B")) : (NQR > 32 ? 256 : 1024);   // queries per launch
     const int NQP = (NQR + 31) / 32 * 32;   // S3P_K: a smaller (cache-resident) centroid table
-    memset(&g_opts, 0, sizeof g_opts);
+    g_opts = flmr_options{};
     std::mt19937 rng(1);
     std::vector<int32_t> codes((size_t)P * L);
     for (auto& c : codes) c = (int32_t)(rng() % K);
@@ -74,11 +80,11 @@ int main(int argc, char** argv) {
     for (int k = 1; k < argc && nimpl < 8; k++) impls[nimpl++] = argv[k];
     if (!nimpl) impls[nimpl++] = "dma";
     for (int v = 0; v < nimpl; v++) {
-        snprintf(g_opts.v[FLMR_OPT_S3_IMPL], sizeof g_opts.v[0], "%s", impls[v]);
+        g_opts.s3 = s3_value(impls[v]);
         CK(hipMemset(d_keys, 0xAB, (size_t)NQ * ND * 8));
         for (int rep = 0; rep < 5; rep++) {
             CK(hipEventRecord(e0, 0));
-            if (flmr_launch_maxsim(a, 0) != 0) { printf("launch failed: %s\n", flmr_err_buf); return 1; }
+            if (flmr_launch_maxsim(a, flmr_s3_choose(a, g_opts), 0) != 0) { printf("launch failed: %s\n", flmr_err_buf); return 1; }
             CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1)); CK(hipGetLastError());
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
             if (rep) printf("S3 (%s): %.3f ms per %d queries (%d rows) x %d finalists\n", impls[v], ms, NQ, NQR, ND);

@@ -224,16 +224,12 @@ __global__ __launch_bounds__(64 * PLAN_WAVES) void cand_plan_kernel(flmr_cand_ar
     const int nl = a.ncell[b], nq = a.nqual[b];
     int32_t* const plan = a.fast_state + FLMR_FAST_HDR + b;
     if (a.s1d_mode && tid == 0) {   // which dense form takes the query, if any (= s1_dense_modes_kernel: one launch less per batch)
-        int m = 0 /* FLMR_S1D_SKIP */, sk = 1;
-        if (!a.hit_valid[b] && !(a.row_ovf && a.row_ovf[b])) {
-            if (nq <= a.s1d_img_rows) m = 1 /* FLMR_S1D_IMAGE */;
-            else if (a.s1d_exact_too) m = 2 /* FLMR_S1D_EXACT */;
-            else sk = 0;   // the scan takes the query
-        }
+        int sk;
+        const int m = flmr_s1_query_form(a.hit_valid[b] || (a.row_ovf && a.row_ovf[b]), nq, a.s1d_img_rows, a.s1d_exact_too, &sk);
         a.s1d_mode[b] = m;
         a.s1d_scan_skip[b] = sk;
-        if (m == 1) atomicOr(a.s1d_any + 0, 1);
-        if (m != 0) atomicOr(a.s1d_any + 1, 1);
+        if (m == FLMR_S1D_IMAGE) atomicOr(a.s1d_any + 0, 1);
+        if (m != FLMR_S1D_SKIP) atomicOr(a.s1d_any + 1, 1);
     }
     if (!a.hit_valid[b] || nl > 512 || nq > 512) {   // (block-uniform) not a list-scatter query / more lists than the fast forms index
         if (tid == 0) *plan = 1;

@@ -35,37 +35,36 @@ extern thread_local char flmr_err_buf[512];
 #define FLMR_LAUNCH_CHECK() FLMR_HIP(hipGetLastError())
 
 // ---- variant switches (A/B runs, cross-check tests) ------------------------------------------------------------------
-// The FLMR_* environment variables are read ONCE per process (first use of the library); afterwards the table changes only
-// through flmr_set_option().  A searcher snapshots the table when it is created and every launch of its batches sees that
-// snapshot (flmr_opt_scope): nothing on the per-batch launch path calls getenv, and the environment cannot flip a running
-// searcher to another kernel path.
-enum flmr_opt_id {
-    FLMR_OPT_S0_IMPL = 0,    // (unset: fp16-split, query-stationary + "hi first" on the sparse path) | qs1 ("hi first" with the dense epilogue inside the loop) | f16 (both products everywhere) | f16rs (row-stationary fp16 kernel) | f32 | mfma | valu
-    FLMR_OPT_FULL_TABLE,     // set: keep the whole centroid-score table
-    FLMR_OPT_CAND_IMPL,      // atomic: first candidate-generation implementation
-    FLMR_OPT_S1_NO_HITMAP,   // set: no hit prefilter
-    FLMR_OPT_S1_IMPL,        // scan: code-scanning stage 1 for every query | slots: the slot form of the scatter kernel for every query (default: its queue form first)
-    FLMR_OPT_S2_IMPL,        // xcda (approximate-then-refine on the sliced kernel: the default where the sliced kernel is) | xcd | walk | lds | ldsb | regs: force the XCD-sliced gather / the dense walk / the LDS-DMA gather (4-wave blocks; 16-wave blocks with the query operand in LDS) / the register gather (default: cost model)
-    FLMR_OPT_S0_STAGED,      // set: staged epilogue for every tile
-    FLMR_OPT_S3_NO_MULTIQ,   // set: single-tile MaxSim kernel for long queries too
-    FLMR_OPT_S3_IMPL,        // lean (default for Nq <= 32: the cw arithmetic on planned tiles) | cw: (c.q + w.q) * 1/norm with table-decoded weights; regs / dma: decompress-normalise-split kernel with register / LDS-DMA row gathers; f32: fp32-MFMA kernel
-    FLMR_OPT_SCORE_IMPL,     // valu: plain-FMA padded scorer
-    FLMR_OPT_POISON,         // set (test runs): every batch starts with its per-query score rows, ranks and survivor lists filled with 0xFF -- a stage that lives off an earlier batch's workspace then produces NaNs / wild indices instead of passing
-    FLMR_OPT_ROW_CAP,        // score rows a searcher keeps per query (64 .. 65535; default 16384, at most K): a query with more centroids above the threshold raises FLMR_ERR_CAPACITY
-    FLMR_OPT_COUNT
-};
+// The FLMR_* environment variables are read and parsed ONCE per process (first use of the library); afterwards the switches
+// change only through flmr_set_option(), which accepts exactly the values below.  A searcher snapshots them when it is created
+// and plans every batch from that snapshot (flmr_plan, flmr_search.hip): nothing on the per-batch launch path calls getenv, and
+// no launcher reads a switch -- each receives the kernel form chosen for it.
+enum class s0_sw : uint8_t { dflt, qs1, f16, f16rs, f32, valu };    // FLMR_S0_IMPL (mfma = f32)
+enum class s1_sw : uint8_t { dflt, scan, slots, image };            // FLMR_S1_IMPL
+enum class s2_sw : uint8_t { dflt, xcda, xcd, walk, lds, regs, ldsb };   // FLMR_S2_IMPL (regs / ldsb: FLMR_EXPERIMENTAL_VARIANTS builds)
+enum class s3_sw : uint8_t { dflt, qs, lean, cw, cwregs, dma, regs, f32 };   // FLMR_S3_IMPL
 struct flmr_options {
-    char v[FLMR_OPT_COUNT][16];
-    bool has(int id) const { return v[id][0] != 0; }
-    bool is(int id, const char* x) const { return strcmp(v[id], x) == 0; }
+    s0_sw s0;                 // unset: fp16-split, query-stationary + "hi first" on the sparse path | qs1 ("hi first" with the dense epilogue
+                              // inside the loop) | f16 (both products everywhere) | f16rs (row-stationary fp16 kernel) | f32 / mfma | valu
+    s1_sw s1;                 // scan: code-scanning stage 1 for every query | slots: the slot form of the scatter kernel for every query
+                              // (default: its queue form first) | image: the queries beyond the dense images go to the scan
+    s2_sw s2;                 // xcda (approximate-then-refine on the sliced kernel: the default where the sliced kernel is) | xcd | walk |
+                              // lds (the LDS-DMA gather) | regs / ldsb (measured losers) -- default: cost model
+    s3_sw s3;                 // lean (default for Nq <= 32) | cw | cwregs | dma | regs (the register maxsim_f16_kernel) | qs (query-stationary
+                              // kernel for long queries) | f32 (fp32-MFMA kernel)
+    bool full_table;          // FLMR_FULL_TABLE: keep the whole centroid-score table
+    bool cand_atomic;         // FLMR_CAND_IMPL=atomic: first candidate-generation implementation
+    bool s1_no_hitmap;        // FLMR_S1_NO_HITMAP: no hit prefilter
+    bool s0_staged;           // FLMR_S0_STAGED: staged epilogue for every tile
+    bool s3_no_multiq;        // FLMR_S3_NO_MULTIQ: single-tile MaxSim kernel for long queries too
+    bool score_valu;          // FLMR_SCORE_IMPL=valu: plain-FMA padded scorer
+    bool poison;              // FLMR_POISON (test runs): every batch starts with its per-query score rows, ranks and survivor lists filled
+                              // with 0xFF -- a stage that lives off an earlier batch's workspace then produces NaNs / wild indices
+    int32_t row_cap;          // FLMR_ROW_CAP: score rows a searcher keeps per query (64 .. 65535; 0 = the default 16384, at most K): a query
+                              // with more centroids above the threshold has its stage 1 recomputed
 };
-const flmr_options& flmr_opts();                        // the active snapshot (searcher scope) or the process table
-const flmr_options& flmr_process_options();             // process table (environment resolved on first use)
-struct flmr_opt_scope {                                 // RAII: launches inside the scope see `o`
-    const flmr_options* prev;
-    explicit flmr_opt_scope(const flmr_options* o);
-    ~flmr_opt_scope();
-};
+// the process switches; FLMR_ERR_INVALID (naming the variable) while the environment holds a value the library does not know
+int flmr_process_options(flmr_options* out);
 
 static inline int64_t flmr_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t flmr_round_up(int64_t a, int64_t b) { return flmr_ceil_div(a, b) * b; }
@@ -129,7 +128,7 @@ struct flmr_index {
     int32_t xcd_round_robin;      // probed at open: workgroup L of a 1-D grid runs on XCD (L % 8) of 8
 };
 int flmr_build_sorted_codes(flmr_index* ix);
-int flmr_build_tiled_centroids(flmr_index* ix);
+int flmr_build_tiled_centroids(flmr_index* ix, bool forced);   // forced: FLMR_S2_IMPL=walk
 int flmr_build_doc_splits(flmr_index* ix);
 int flmr_build_s3_tables(flmr_index* ix);   // wtab16 + inv_norm (optional: left NULL when they cannot be built)
 
@@ -150,7 +149,7 @@ struct flmr_s0_args {
     int32_t idx_words;
     float* part_val;         // [nqueries, nblk, ncol, ncells]
     int32_t* part_idx;
-    int32_t nblk;            // number of partial-list row blocks (set by flmr_launch_centroid_scores for the kernel it picks)
+    int32_t nblk;            // number of partial-list row blocks (flmr_s0_choose: for the kernel it picks)
     int32_t* cells;          // [nqueries, max_cells]
     int32_t* ncell;          // [nqueries]
     int32_t max_cells;
@@ -170,13 +169,21 @@ struct flmr_s0_args {
                              // approximate-then-refine form reads it too); q_err == q_err_buf when stage 0 itself uses the bound
     float* q_err_sum;        // [nqueries] bound on |approximate - full| for a passage's stage-2 score (sum over the columns + summation rounding)
     float cen_norm_max;      // >= max_c ||c||_2
-    int32_t grp_blocks;      // set by flmr_launch_centroid_scores: > 0 = the kernel it picked ALSO left one column maximum per `grp_blocks`
+    int32_t grp_blocks;      // flmr_s0_choose: > 0 = the kernel it picked ALSO leaves one column maximum per `grp_blocks`
                              // consecutive 64-row blocks, as floats [nqueries, nblk / grp_blocks, ncol] in the part_idx buffer (unused on
                              // that path): s0_select_cells reads those first and only the best groups' block maxima after them
 };
-int flmr_launch_centroid_scores(flmr_s0_args& a, hipStream_t st);
+// stage-0 kernel forms: query-stationary (qs2: "hi first" / fp16 numerics; qs), row-stationary fp16 (sparse table / whole table), fp32
+// MFMA, plain FMA
+enum class s0_form : uint8_t { qs2, qs, f16_sparse, f16_table, f32, valu };
+struct flmr_s0_choice {
+    s0_form form;
+    int32_t nblk, part_rows, grp_blocks;   // the partial-list geometry of that form (flmr_s0_args fields of the same names)
+};
+flmr_s0_choice flmr_s0_choose(const flmr_s0_args& a, const flmr_options& o);
+int flmr_launch_centroid_scores(const flmr_s0_args& a, s0_form form, hipStream_t st);
 int flmr_launch_select_cells(const flmr_s0_args& a, hipStream_t st);
-int flmr_launch_centroid_argmax(flmr_s0_args& a, int32_t* out_codes, hipStream_t st);  // index build: nearest centroid per column
+int flmr_launch_centroid_argmax(flmr_s0_args a, int32_t* out_codes, hipStream_t st);  // index build: nearest centroid per column
 int flmr_launch_split_q(const flmr_s0_args& a, hipStream_t st);  // q_hi / q_lo images only (query-split stage 0)
 int flmr_check_f16_exact(const float* dev, size_t n, int32_t* host_result);
 int flmr_convert_f16(const float* dev, size_t n, _Float16* out);
@@ -258,9 +265,10 @@ int flmr_launch_filter_stage2(const flmr_filter_args& f, const int32_t* pids, in
                               const int32_t* counts, int32_t max_count, uint64_t* keys, int64_t key_stride,
                               hipStream_t st);
 // stage 2 without the score table: recompute the survivors' centroid scores from the fp16 centroids (bitwise = S0)
+// (form: lds = the LDS-DMA gather; regs / ldsb = the measured losers of FLMR_EXPERIMENTAL_VARIANTS builds)
 int flmr_launch_filter_stage2_mfma(const flmr_filter_args& f, const int32_t* pids, int64_t pid_stride, const int32_t* counts,
                                    int32_t max_count, uint64_t* keys, int64_t key_stride, const _Float16* cen16,
-                                   const _Float16* q_hi, const _Float16* q_lo, hipStream_t st);
+                                   const _Float16* q_hi, const _Float16* q_lo, s2_sw form, hipStream_t st);
 // stage 2 as a query-stationary dense walk over the centroid table (flmr_stage2_walk.hip): same keys, bit for bit
 int flmr_launch_filter_stage2_walk(const flmr_filter_args& f, const int32_t* pids, int64_t pid_stride, const int32_t* counts,
                                    int32_t max_count, uint64_t* keys, int64_t key_stride, const _Float16* cen16,
@@ -339,7 +347,12 @@ struct flmr_maxsim_args {
     float* colmax_ws;         // long queries: [nqueries, key_stride, round_up(nq, 32)] per-passage column maxima (nullable)
     int64_t colmax_cap;       // floats
 };
-int flmr_launch_maxsim(const flmr_maxsim_args& a, hipStream_t st);
+// stage-3 kernel forms (flmr_maxsim.hip): query-stationary on planned tiles (long queries), multi-tile, planned tiles ("lean"),
+// centroid + weight on the LDS-DMA pipeline, the same with register gathers, LDS-DMA decompress, register decompress
+// (maxsim_f16_kernel), fp32 MFMA; the fp16-numerics pipeline / its plain form
+enum class s3_form : uint8_t { qs, multiq, lean, cw, cwregs, dma, regs, f32, gpu_tuned, gpu_plain };
+s3_form flmr_s3_choose(const flmr_maxsim_args& a, const flmr_options& o);
+int flmr_launch_maxsim(const flmr_maxsim_args& a, s3_form form, hipStream_t st);
 
 // ---- stage 1 for dense survivor sets (flmr_stage1_dense.hip) ----
 struct flmr_s1d_args {

@@ -8,6 +8,18 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define FLMR_NEG_INF (-__builtin_huge_valf())
 
+// Stage 1 of a query the list-scatter forms left (cand_plan_kernel, s1_dense_modes_kernel): `taken` = the list scatter or the
+// recompute form has it; else the dense image form where its surviving centroids fit the images (img_rows > 0: the form runs in this
+// batch), else the dense exact form when it runs, else the scan.  Returns FLMR_S1D_*; *scan_skip = 0 only for the scan's queries.
+__device__ __forceinline__ int flmr_s1_query_form(bool taken, int32_t nqual, int32_t img_rows, int32_t exact_too, int32_t* scan_skip) {
+    *scan_skip = 1;
+    if (taken) return FLMR_S1D_SKIP;
+    if (img_rows > 0 && nqual <= img_rows) return FLMR_S1D_IMAGE;
+    if (exact_too) return FLMR_S1D_EXACT;
+    *scan_skip = 0;
+    return FLMR_S1D_SKIP;
+}
+
 // ---- wave reductions by DPP (row maxima / minima: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror; the four rows
 // through the scalar unit): ~10 instructions and no LDS round trip, against 6 x ds_bpermute for a shuffle butterfly ----------
 __device__ __forceinline__ float flmr_wave_max_f32(float x) {

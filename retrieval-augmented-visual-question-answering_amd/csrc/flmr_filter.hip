@@ -870,9 +870,12 @@ __global__ __launch_bounds__(64 * WAVES, B_LDS ? 1 : 2) void filter_stage2_lds_k
 
 int flmr_launch_filter_stage2_mfma(const flmr_filter_args& f, const int32_t* pids, int64_t pid_stride, const int32_t* counts,
                                    int32_t max_count, uint64_t* keys, int64_t key_stride, const _Float16* cen16,
-                                   const _Float16* q_hi, const _Float16* q_lo, hipStream_t st) {
+                                   const _Float16* q_hi, const _Float16* q_lo, s2_sw form, hipStream_t st) {
     if (max_count <= 0) return FLMR_OK;
     if (f.ncol != 32) FLMR_FAIL(FLMR_ERR_INVALID, "stage-2 recompute needs one column tile");
+#ifndef FLMR_EXPERIMENTAL_VARIANTS
+    if (form == s2_sw::regs || form == s2_sw::ldsb) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the regs / ldsb stage-2 gathers need a FLMR_EXPERIMENTAL_VARIANTS build");
+#endif
     int G = (int)flmr_ceil_div(8192, 4 * (int64_t)f.nqueries);
     const int gmin = (int)flmr_ceil_div(max_count, 4 * 64);
     if (G < gmin) G = gmin;
@@ -882,10 +885,10 @@ int flmr_launch_filter_stage2_mfma(const flmr_filter_args& f, const int32_t* pid
     // Measured losers, compiled only into a -DFLMR_EXPERIMENTAL_VARIANTS library (profiles/build_variant.py):
     // FLMR_S2_IMPL=regs: the first form of the kernel (per-lane half-row gathers into registers);
     // FLMR_S2_IMPL=ldsb: 16-wave blocks with the query operand in LDS (5.6 ms against 4.1 ms)
-    if (flmr_opts().is(FLMR_OPT_S2_IMPL, "regs"))
+    if (form == s2_sw::regs)
         hipLaunchKernelGGL(filter_stage2_mfma_kernel, dim3(f.nqueries, G), dim3(256), 4 * 33 * sizeof(float), st, f, pids, pid_stride,
                            counts, keys, key_stride, cen16, q_hi, q_lo);
-    else if (flmr_opts().is(FLMR_OPT_S2_IMPL, "ldsb")) {
+    else if (form == s2_sw::ldsb) {
         // 16-wave blocks sharing the query operand through LDS
         int G16 = (int)flmr_ceil_div(8192, 16 * (int64_t)f.nqueries);
         const int g16min = (int)flmr_ceil_div(max_count, 16 * 64);

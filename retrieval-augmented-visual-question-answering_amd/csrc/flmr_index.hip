@@ -10,37 +10,126 @@
 
 thread_local char flmr_err_buf[512] = {0};
 
-static const char* kOptNames[FLMR_OPT_COUNT] = {"FLMR_S0_IMPL", "FLMR_FULL_TABLE", "FLMR_CAND_IMPL", "FLMR_S1_NO_HITMAP",
-                                                 "FLMR_S1_IMPL", "FLMR_S2_IMPL", "FLMR_S0_STAGED", "FLMR_S3_NO_MULTIQ",
-                                                 "FLMR_S3_IMPL", "FLMR_SCORE_IMPL", "FLMR_POISON", "FLMR_ROW_CAP"};
-static flmr_options g_opts;
-static std::once_flag g_opts_once;
-static thread_local const flmr_options* t_active_opts = nullptr;
+// ---- variant switches: parsed once from the environment, then changed only by flmr_set_option ----------------------------
+// One entry per switch: its name, the accepted values (NULL: a set-or-unset flag, "#": an integer) and where a value lands.
+struct opt_value { const char* name; int v; };
+struct opt_spec { const char* name; const opt_value* values; int nvalues; };
+static const opt_value kS0[] = {{"qs1", (int)s0_sw::qs1}, {"f16", (int)s0_sw::f16}, {"f16rs", (int)s0_sw::f16rs},
+                                {"f32", (int)s0_sw::f32}, {"mfma", (int)s0_sw::f32}, {"valu", (int)s0_sw::valu}};
+static const opt_value kS1[] = {{"scan", (int)s1_sw::scan}, {"slots", (int)s1_sw::slots}, {"image", (int)s1_sw::image}};
+static const opt_value kS2[] = {{"xcda", (int)s2_sw::xcda}, {"xcd", (int)s2_sw::xcd}, {"walk", (int)s2_sw::walk}, {"lds", (int)s2_sw::lds},
+#ifdef FLMR_EXPERIMENTAL_VARIANTS
+                                {"regs", (int)s2_sw::regs}, {"ldsb", (int)s2_sw::ldsb},
+#endif
+};
+static const opt_value kS3[] = {{"qs", (int)s3_sw::qs}, {"lean", (int)s3_sw::lean}, {"cw", (int)s3_sw::cw}, {"cwregs", (int)s3_sw::cwregs},
+                                {"dma", (int)s3_sw::dma}, {"regs", (int)s3_sw::regs}, {"f32", (int)s3_sw::f32}};
+static const opt_value kAtomic[] = {{"atomic", 1}};
+static const opt_value kValu[] = {{"valu", 1}};
+static const opt_value kInt[] = {{"#", 0}};
+#define N_(a) (int)(sizeof(a) / sizeof(a[0]))
+enum { O_S0, O_FULL_TABLE, O_CAND, O_NO_HITMAP, O_S1, O_S2, O_S0_STAGED, O_NO_MULTIQ, O_S3, O_SCORE, O_POISON, O_ROW_CAP, O_COUNT };
+static const opt_spec kOpts[O_COUNT] = {
+    {"FLMR_S0_IMPL", kS0, N_(kS0)}, {"FLMR_FULL_TABLE", nullptr, 0}, {"FLMR_CAND_IMPL", kAtomic, 1}, {"FLMR_S1_NO_HITMAP", nullptr, 0},
+    {"FLMR_S1_IMPL", kS1, N_(kS1)}, {"FLMR_S2_IMPL", kS2, N_(kS2)}, {"FLMR_S0_STAGED", nullptr, 0}, {"FLMR_S3_NO_MULTIQ", nullptr, 0},
+    {"FLMR_S3_IMPL", kS3, N_(kS3)}, {"FLMR_SCORE_IMPL", kValu, 1}, {"FLMR_POISON", nullptr, 0}, {"FLMR_ROW_CAP", kInt, 1}};
+#undef N_
 
-static void opts_from_env() {
-    memset(&g_opts, 0, sizeof(g_opts));
-    for (int i = 0; i < FLMR_OPT_COUNT; i++) {
-        const char* e = getenv(kOptNames[i]);
-        if (e) snprintf(g_opts.v[i], sizeof(g_opts.v[i]), "%s", e[0] ? e : "1");
+static flmr_options g_opts;
+static char g_env_err[O_COUNT][160];   // a value in the environment the library does not know ("" = none)
+static std::once_flag g_opts_once;
+
+// value (non-empty) -> the switch's field; FLMR_ERR_INVALID with the accepted values in `err`
+static int parse_opt(int id, const char* value, flmr_options* o, char* err, size_t errlen) {
+    const opt_spec& sp = kOpts[id];
+    int v = 1;
+    if (sp.values && sp.values[0].name[0] == '#') {
+        char* end = nullptr;
+        const long x = strtol(value, &end, 10);
+        if (end == value || *end != 0) {
+            snprintf(err, errlen, "%s=%s: expected an integer (score rows per query, 64 .. 65535)", sp.name, value);
+            return FLMR_ERR_INVALID;
+        }
+        v = x < 64 ? 64 : x > 65535 ? 65535 : (int)x;
+    } else if (sp.values) {
+        int i = 0;
+        while (i < sp.nvalues && strcmp(value, sp.values[i].name) != 0) i++;
+        if (i == sp.nvalues) {
+            int n = snprintf(err, errlen, "%s=%s: accepted values:", sp.name, value);
+            for (int j = 0; j < sp.nvalues && n > 0 && (size_t)n < errlen; j++) n += snprintf(err + n, errlen - n, " %s", sp.values[j].name);
+            return FLMR_ERR_INVALID;
+        }
+        v = sp.values[i].v;
+    }
+    switch (id) {
+        case O_S0: o->s0 = (s0_sw)v; break;
+        case O_FULL_TABLE: o->full_table = true; break;
+        case O_CAND: o->cand_atomic = true; break;
+        case O_NO_HITMAP: o->s1_no_hitmap = true; break;
+        case O_S1: o->s1 = (s1_sw)v; break;
+        case O_S2: o->s2 = (s2_sw)v; break;
+        case O_S0_STAGED: o->s0_staged = true; break;
+        case O_NO_MULTIQ: o->s3_no_multiq = true; break;
+        case O_S3: o->s3 = (s3_sw)v; break;
+        case O_SCORE: o->score_valu = true; break;
+        case O_POISON: o->poison = true; break;
+        default: o->row_cap = v; break;
+    }
+    return FLMR_OK;
+}
+
+// the switch's field back to its unset state
+static void clear_opt(int id, flmr_options* o) {
+    flmr_options d{};
+    switch (id) {
+        case O_S0: o->s0 = d.s0; break;
+        case O_FULL_TABLE: o->full_table = false; break;
+        case O_CAND: o->cand_atomic = false; break;
+        case O_NO_HITMAP: o->s1_no_hitmap = false; break;
+        case O_S1: o->s1 = d.s1; break;
+        case O_S2: o->s2 = d.s2; break;
+        case O_S0_STAGED: o->s0_staged = false; break;
+        case O_NO_MULTIQ: o->s3_no_multiq = false; break;
+        case O_S3: o->s3 = d.s3; break;
+        case O_SCORE: o->score_valu = false; break;
+        case O_POISON: o->poison = false; break;
+        default: o->row_cap = 0; break;
     }
 }
-const flmr_options& flmr_process_options() {
-    std::call_once(g_opts_once, opts_from_env);
-    return g_opts;
+
+static void opts_from_env() {
+    g_opts = flmr_options{};
+    for (int i = 0; i < O_COUNT; i++) {
+        g_env_err[i][0] = 0;
+        const char* e = getenv(kOpts[i].name);
+        if (e) (void)parse_opt(i, e[0] ? e : "1", &g_opts, g_env_err[i], sizeof(g_env_err[i]));
+    }
 }
-const flmr_options& flmr_opts() { return t_active_opts ? *t_active_opts : flmr_process_options(); }
-flmr_opt_scope::flmr_opt_scope(const flmr_options* o) : prev(t_active_opts) { t_active_opts = o; }
-flmr_opt_scope::~flmr_opt_scope() { t_active_opts = prev; }
+
+int flmr_process_options(flmr_options* out) {
+    std::call_once(g_opts_once, opts_from_env);
+    for (int i = 0; i < O_COUNT; i++)
+        if (g_env_err[i][0]) FLMR_FAIL(FLMR_ERR_INVALID, "environment variable %s", g_env_err[i]);
+    *out = g_opts;
+    return FLMR_OK;
+}
 
 // name = one of the FLMR_* switch names; value NULL or "" clears it.  Affects op-level calls at once and searchers
 // created afterwards (existing searchers keep the snapshot taken at flmr_searcher_create).
 extern "C" int flmr_set_option(const char* name, const char* value) {
     if (!name) FLMR_FAIL(FLMR_ERR_INVALID, "name is NULL");
-    (void)flmr_process_options();
-    for (int i = 0; i < FLMR_OPT_COUNT; i++)
-        if (strcmp(name, kOptNames[i]) == 0) {
-            if (value && strlen(value) >= sizeof(g_opts.v[i])) FLMR_FAIL(FLMR_ERR_INVALID, "value too long for %s", name);
-            snprintf(g_opts.v[i], sizeof(g_opts.v[i]), "%s", value ? value : "");
+    std::call_once(g_opts_once, opts_from_env);
+    for (int i = 0; i < O_COUNT; i++)
+        if (strcmp(name, kOpts[i].name) == 0) {
+            if (!value || !value[0]) {
+                clear_opt(i, &g_opts);
+            } else {
+                flmr_options o = g_opts;
+                const int rc = parse_opt(i, value, &o, flmr_err_buf, sizeof(flmr_err_buf));
+                if (rc) return rc;
+                g_opts = o;
+            }
+            g_env_err[i][0] = 0;
             return FLMR_OK;
         }
     FLMR_FAIL(FLMR_ERR_INVALID, "unknown option %s", name);
@@ -109,8 +198,11 @@ extern "C" int flmr_index_open(const flmr_index_desc_t* d, flmr_index_t** out) {
     if (!d->codes || !d->residuals || !d->doc_offsets || !d->ivf_pids || !d->ivf_offsets || !d->centroids ||
         !d->bucket_weights)
         FLMR_FAIL(FLMR_ERR_INVALID, "NULL array in descriptor");
+    flmr_options opt;   // (FLMR_S2_IMPL=walk builds the walk's table on any index)
+    int rc = flmr_process_options(&opt);
+    if (rc) return rc;
     int ndev = 0;
-    int rc = flmr_device_count(&ndev);
+    rc = flmr_device_count(&ndev);
     if (rc) return rc;
 
     flmr_index* ix = new (std::nothrow) flmr_index();
@@ -170,7 +262,7 @@ extern "C" int flmr_index_open(const flmr_index_desc_t* d, flmr_index_t** out) {
         FLMR_TRY(flmr_convert_f16(ix->centroids, (size_t)K * FLMR_DIM, ix->centroids_f16));
     }
     FLMR_TRY(flmr_build_sorted_codes(ix));
-    FLMR_TRY(flmr_build_tiled_centroids(ix));
+    FLMR_TRY(flmr_build_tiled_centroids(ix, opt.s2 == s2_sw::walk));
     FLMR_TRY(flmr_build_doc_splits(ix));
     FLMR_TRY(flmr_build_chunk_table(ix->ivf_pids, ix->ivf_offsets, K, ix->num_passages, &ix->ivf_chunk_tab, &ix->nchunks));
     // fused decode table (always built on the host from the host bucket_weights)

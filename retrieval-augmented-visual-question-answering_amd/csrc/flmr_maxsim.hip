@@ -2135,29 +2135,8 @@ static int launch_maxsim_qs_t(const flmr_maxsim_args& a, hipStream_t st, int nqp
 #endif
 }
 
-template <int NBITS>
-static int launch_maxsim_f16_t(const flmr_maxsim_args& a, hipStream_t st) {
-    const flmr_index* ix = a.ix;
-    const int nqp = (int)flmr_round_up(a.nq, 32);
-    const size_t lds = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)4 * nqp * sizeof(float);
-    if (lds > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large for the MaxSim kernel's LDS column maxima", a.nq);
-    // long queries: the query-stationary kernel on planned tiles (below ~6 q-tiles most of a workgroup's waves would hold no query
-    // rows: the chunked kernel stays); it splits the query itself (other scaling)
-    const bool use_qs = (nqp >= S3Q_MIN_NQP || (nqp > 32 && flmr_opts().is(FLMR_OPT_S3_IMPL, "qs"))) && !flmr_opts().has(FLMR_OPT_S3_NO_MULTIQ) &&
-        ix->inv_norm && a.plan_desc && a.plan_wbeg && a.colmax_ws && a.colmax_cap >= (int64_t)a.nqueries * a.key_stride * nqp + a.nqueries && ix->N >= 32 &&
-        ix->N < ((int64_t)1 << 32) && ((size_t)ix->K * 256 < ((size_t)1 << 32)) && a.max_count <= S3L_MAX_DOCS && a.plan_wcap >= 2 &&
-        a.plan_stride >= (int64_t)a.max_count * ((ix->max_doclen + 31) / 32) &&
-        (flmr_opts().is(FLMR_OPT_S3_IMPL, "qs") || !flmr_opts().has(FLMR_OPT_S3_IMPL));
-    if (use_qs) {
-        const int rc = launch_maxsim_qs_t<NBITS>(a, st, nqp);
-        if (rc) return rc;
-        FLMR_LAUNCH_CHECK();
-        return FLMR_OK;
-    }
-    if (!a.q_split_done)
-        hipLaunchKernelGGL(s3_split_q, dim3((nqp * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq, nqp,
-                           a.q_hi, a.q_lo);
-    // waves per query: enough to fill the chip, at most 64 documents per wave, at least 1
+// waves per query of the one-tile kernels: enough to fill the chip, at most 64 documents per wave, at least 1
+static int s3_waves(const flmr_maxsim_args& a) {
     int G = (int)flmr_ceil_div(4096, 4 * (int64_t)a.nqueries);
     const int gmin = (int)flmr_ceil_div(a.max_count, 4 * 64);
     if (G < gmin) G = gmin;
@@ -2166,7 +2145,70 @@ static int launch_maxsim_f16_t(const flmr_maxsim_args& a, hipStream_t st) {
 #ifdef S3L_G
     G = S3L_G;
 #endif
-    if (nqp > 32 && !flmr_opts().has(FLMR_OPT_S3_NO_MULTIQ)) {
+    return G;
+}
+
+// what each form needs of the index and the workspace (the planned-tile forms: the plan's descriptors; the cw forms: the S3 tables)
+static bool s3_planned_ok(const flmr_maxsim_args& a) {
+    const flmr_index* ix = a.ix;
+    return ix->inv_norm && a.plan_desc && a.plan_wbeg && ix->N >= 32 && ix->N < ((int64_t)1 << 32) && ((size_t)ix->K * 256 < ((size_t)1 << 32)) &&
+           a.max_count <= S3L_MAX_DOCS && a.plan_stride >= (int64_t)a.max_count * ((ix->max_doclen + 31) / 32);
+}
+static bool s3_qs_ok(const flmr_maxsim_args& a, int nqp) {
+    return s3_planned_ok(a) && a.colmax_ws && a.colmax_cap >= (int64_t)a.nqueries * a.key_stride * nqp + a.nqueries && a.plan_wcap >= 2;
+}
+static bool s3_lean_ok(const flmr_maxsim_args& a) {
+    return s3_planned_ok(a) && a.ix->wtab16 && a.plan_wcap >= 4 * s3_waves(a) + 1;
+}
+static bool s3_cw_ok(const flmr_maxsim_args& a) {
+    return a.ix->inv_norm && a.ix->wtab16 && ((size_t)a.ix->K * 256 < ((size_t)1 << 32));
+}
+
+// Stage-3 form.  fp16-exact centroids and split buffers: long queries on the query-stationary kernel from S3Q_MIN_NQP rows (below ~6
+// q-tiles most of a workgroup's waves would hold no query rows: the multi-tile kernel stays), one query tile on planned tiles, else
+// the centroid + weight form; FLMR_S3_IMPL picks another one-tile form (or qs below S3Q_MIN_NQP), FLMR_S3_NO_MULTIQ the one-tile
+// kernels for long queries, f32 the fp32 kernel.  The fp16-numerics mode: its wave-per-document pipeline for one query tile.
+s3_form flmr_s3_choose(const flmr_maxsim_args& a, const flmr_options& o) {
+    const flmr_index* ix = a.ix;
+    if (a.gpu_fp16) return (a.nq <= 32 && ix->centroids_f16 && a.q_hi && a.q_lo && o.s3 != s3_sw::f32) ? s3_form::gpu_tuned : s3_form::gpu_plain;
+    if (!(ix->centroids_f16_exact && ix->centroids_f16 && a.q_hi && a.q_lo && o.s3 != s3_sw::f32)) return s3_form::f32;
+    const int nqp = (int)flmr_round_up(a.nq, 32);
+    const bool any = o.s3 == s3_sw::dflt;
+    if ((nqp >= S3Q_MIN_NQP || (nqp > 32 && o.s3 == s3_sw::qs)) && !o.s3_no_multiq && s3_qs_ok(a, nqp) && (o.s3 == s3_sw::qs || any))
+        return s3_form::qs;
+    if (nqp > 32 && !o.s3_no_multiq) return s3_form::multiq;
+    if (nqp != 32) return s3_form::regs;
+    if (s3_lean_ok(a) && (o.s3 == s3_sw::lean || any)) return s3_form::lean;
+    if (s3_cw_ok(a) && (o.s3 == s3_sw::cw || o.s3 == s3_sw::lean || any)) return s3_form::cw;
+    if (ix->inv_norm && ix->wtab16 && o.s3 == s3_sw::cwregs) return s3_form::cwregs;
+    if (((size_t)ix->K * 256 < ((size_t)1 << 32)) && o.s3 == s3_sw::dma) return s3_form::dma;
+    return s3_form::regs;
+}
+
+template <int NBITS>
+static int launch_maxsim_f16_t(const flmr_maxsim_args& a, s3_form form, hipStream_t st) {
+    const flmr_index* ix = a.ix;
+    const int nqp = (int)flmr_round_up(a.nq, 32);
+    const size_t lds = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)4 * nqp * sizeof(float);
+    if (lds > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large for the MaxSim kernel's LDS column maxima", a.nq);
+    if (!(ix->centroids_f16_exact && ix->centroids_f16 && a.q_hi && a.q_lo))
+        FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the fp16 MaxSim kernels need fp16-exact centroids and split buffers");
+    const bool one_tile = form != s3_form::qs && form != s3_form::multiq && form != s3_form::regs;
+    if ((one_tile && nqp != 32) || (form == s3_form::multiq && nqp <= 32) || (form == s3_form::qs && (nqp <= 32 || !s3_qs_ok(a, nqp))) ||
+        (form == s3_form::lean && !s3_lean_ok(a)) || (form == s3_form::cw && !s3_cw_ok(a)) ||
+        (form == s3_form::cwregs && !(ix->inv_norm && ix->wtab16)) || (form == s3_form::dma && (size_t)ix->K * 256 >= ((size_t)1 << 32)))
+        FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "stage-3 form %d does not run on this index / workspace / nq=%d", (int)form, a.nq);
+    if (form == s3_form::qs) {
+        const int rc = launch_maxsim_qs_t<NBITS>(a, st, nqp);
+        if (rc) return rc;
+        FLMR_LAUNCH_CHECK();
+        return FLMR_OK;
+    }
+    if (!a.q_split_done)
+        hipLaunchKernelGGL(s3_split_q, dim3((nqp * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq, nqp,
+                           a.q_hi, a.q_lo);
+    const int G = s3_waves(a);
+    if (form == s3_form::multiq) {
         const size_t lds2 = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)S3_QC * 2 * 32 * S3_BROW * sizeof(_Float16) +
                             (size_t)S3_MQW * (32 * S3_QC + 64) * sizeof(float);
         int G2 = (int)flmr_ceil_div(4096, S3_MQW * (int64_t)a.nqueries);
@@ -2178,15 +2220,11 @@ static int launch_maxsim_f16_t(const flmr_maxsim_args& a, hipStream_t st) {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
         hipLaunchKernelGGL(maxsim_f16_multiq_kernel<NBITS>, dim3(a.nqueries, G2), dim3(64 * S3_MQW), lds2, st, a, ix->codes,
                            ix->residuals, ix->doc_offsets, ix->centroids_f16, ix->wlut, nqp);
-    } else if (nqp == 32 && ix->inv_norm && ix->wtab16 && ((size_t)ix->K * 256 < ((size_t)1 << 32)) && a.plan_desc && a.plan_wbeg &&
-               ix->N >= 32 && ix->N < ((int64_t)1 << 32) && a.max_count <= S3L_MAX_DOCS && a.plan_wcap >= 4 * G + 1 &&
-               a.plan_stride >= (int64_t)a.max_count * ((ix->max_doclen + 31) / 32) &&
-               (flmr_opts().is(FLMR_OPT_S3_IMPL, "lean") || !flmr_opts().has(FLMR_OPT_S3_IMPL))) {
+    } else if (form == s3_form::lean) {
         // planned tiles (the default for one query tile)
         const int rc = launch_maxsim_lean_t<NBITS>(a, st, G);
         if (rc) return rc;
-    } else if (nqp == 32 && ix->inv_norm && ix->wtab16 && ((size_t)ix->K * 256 < ((size_t)1 << 32)) &&
-               (flmr_opts().is(FLMR_OPT_S3_IMPL, "cw") || flmr_opts().is(FLMR_OPT_S3_IMPL, "lean") || !flmr_opts().has(FLMR_OPT_S3_IMPL))) {
+    } else if (form == s3_form::cw) {
         // centroid + weight form on the LDS-DMA pipeline (the default for one query tile; 32-bit row offsets: table < 4 GB)
         const size_t tabw = NBITS == 8 ? 256 : 256 * (8 / NBITS);
 #ifdef S3_LDS_PAD   // development probe: a larger request leaves one workgroup per CU (one wave per SIMD)
@@ -2198,12 +2236,12 @@ static int launch_maxsim_f16_t(const flmr_maxsim_args& a, hipStream_t st) {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
         hipLaunchKernelGGL((maxsim_f16_dma_kernel<NBITS, true>), dim3(a.nqueries, G), dim3(256), lds4, st, a, ix->codes, ix->residuals,
                            ix->doc_offsets, ix->centroids_f16, reinterpret_cast<const float*>(ix->wtab16), nqp, ix->inv_norm);
-    } else if (nqp == 32 && ix->inv_norm && ix->wtab16 && flmr_opts().is(FLMR_OPT_S3_IMPL, "cwregs")) {
+    } else if (form == s3_form::cwregs) {
         // the same arithmetic with register row gathers, one tile in flight (A/B runs; bit-identical to the default)
         const size_t lds4 = (size_t)(NBITS == 8 ? 1024 : 2 * 512 * (8 / NBITS)) + (size_t)4 * 64 * sizeof(float);
         hipLaunchKernelGGL(maxsim_cw_kernel<NBITS>, dim3(a.nqueries, G), dim3(256), lds4, st, a, ix->codes, ix->residuals,
                            ix->doc_offsets, ix->centroids_f16, ix->wtab16, ix->inv_norm);
-    } else if (nqp == 32 && ((size_t)ix->K * 256 < ((size_t)1 << 32)) && flmr_opts().is(FLMR_OPT_S3_IMPL, "dma")) {
+    } else if (form == s3_form::dma) {
         // (measured, 1 M passages: nbits = 2  2.03 vs 2.04 ms for the register form; nbits = 8  2.31 vs 2.43 ms)
         const size_t lds3 = (((size_t)256 * (8 / NBITS) + (size_t)4 * (nqp + 32)) * sizeof(float) + 15) / 16 * 16 + 4 * 16384 + 4 * 2048;
         FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(maxsim_f16_dma_kernel<NBITS, false>),
@@ -2346,37 +2384,22 @@ int flmr_build_s3_tables(flmr_index* ix) {
     return FLMR_OK;
 }
 
-// FLMR_S3_IMPL = f16 (default when the centroids are fp16-exact and split buffers are supplied) | f32
-int flmr_launch_maxsim(const flmr_maxsim_args& a, hipStream_t st) {
+int flmr_launch_maxsim(const flmr_maxsim_args& a, s3_form form, hipStream_t st) {
     if (a.max_count <= 0) return FLMR_OK;
-    if (a.gpu_fp16) {
-        // one query tile, fp16 centroid copy and split buffers at hand: the wave-per-document pipeline; else (long queries,
-        // FLMR_S3_IMPL=f32) the plain one-workgroup-per-passage kernel with the same arithmetic
-        const bool tuned = a.nq <= 32 && a.ix->centroids_f16 && a.q_hi && a.q_lo && !flmr_opts().is(FLMR_OPT_S3_IMPL, "f32");
-        switch (a.ix->nbits) {
-            case 1: return tuned ? launch_maxsim_f16_gpunum_t<1>(a, st) : launch_maxsim_gpu_fp16_t<1>(a, st);
-            case 2: return tuned ? launch_maxsim_f16_gpunum_t<2>(a, st) : launch_maxsim_gpu_fp16_t<2>(a, st);
-            case 4: return tuned ? launch_maxsim_f16_gpunum_t<4>(a, st) : launch_maxsim_gpu_fp16_t<4>(a, st);
-            case 8: return tuned ? launch_maxsim_f16_gpunum_t<8>(a, st) : launch_maxsim_gpu_fp16_t<8>(a, st);
-        }
-        FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nbits=%d", a.ix->nbits);
+    if (a.ix->nbits != 1 && a.ix->nbits != 2 && a.ix->nbits != 4 && a.ix->nbits != 8) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nbits=%d", a.ix->nbits);
+    if ((form == s3_form::gpu_tuned || form == s3_form::gpu_plain) != (a.gpu_fp16 != 0))
+        FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "stage-3 form %d in the %s numerics mode", (int)form, a.gpu_fp16 ? "fp16" : "CPU-path");
+#define S3_NB(fn) (a.ix->nbits == 1 ? fn<1> : a.ix->nbits == 2 ? fn<2> : a.ix->nbits == 4 ? fn<4> : fn<8>)
+    switch (form) {
+        case s3_form::gpu_tuned:
+            // one query tile, fp16 centroid copy and split buffers at hand: the wave-per-document pipeline
+            if (!(a.nq <= 32 && a.ix->centroids_f16 && a.q_hi && a.q_lo)) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the fp16-numerics MaxSim pipeline needs one query tile and split buffers");
+            return S3_NB(launch_maxsim_f16_gpunum_t)(a, st);
+        case s3_form::gpu_plain: return S3_NB(launch_maxsim_gpu_fp16_t)(a, st);   // (long queries, FLMR_S3_IMPL=f32: one workgroup per passage)
+        case s3_form::f32: return S3_NB(launch_maxsim_t)(a, st);
+        default: return S3_NB(launch_maxsim_f16_t)(a, form, st);
     }
-    const bool f16 = a.ix->centroids_f16_exact && a.ix->centroids_f16 && a.q_hi && a.q_lo && !flmr_opts().is(FLMR_OPT_S3_IMPL, "f32");
-    if (f16) {
-        switch (a.ix->nbits) {
-            case 1: return launch_maxsim_f16_t<1>(a, st);
-            case 2: return launch_maxsim_f16_t<2>(a, st);
-            case 4: return launch_maxsim_f16_t<4>(a, st);
-            case 8: return launch_maxsim_f16_t<8>(a, st);
-        }
-    }
-    switch (a.ix->nbits) {
-        case 1: return launch_maxsim_t<1>(a, st);
-        case 2: return launch_maxsim_t<2>(a, st);
-        case 4: return launch_maxsim_t<4>(a, st);
-        case 8: return launch_maxsim_t<8>(a, st);
-    }
-    FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nbits=%d", a.ix->nbits);
+#undef S3_NB
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -200,6 +200,8 @@ extern "C" int flmr_score_pids(const flmr_index_t* ix, const float* Q, int32_t n
                                float* out, flmr_stream_t stream) {
     if (!ix || !Q || !pids || !out) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     if (npids <= 0) return FLMR_OK;
+    flmr_options opt;
+    RUN(flmr_process_options(&opt));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     scratch sc;
     int32_t* cnt;
@@ -229,7 +231,7 @@ extern "C" int flmr_score_pids(const flmr_index_t* ix, const float* Q, int32_t n
             }
         }
     }
-    RUN(flmr_launch_maxsim(m, st));
+    RUN(flmr_launch_maxsim(m, flmr_s3_choose(m, opt), st));
     FLMR_HIP(hipStreamSynchronize(st));
     return FLMR_OK;
 }
@@ -430,8 +432,17 @@ __global__ __launch_bounds__(256, 2) void colbert_score_padded_mfma_kernel(const
 }
 
 // cross: Q holds q_batch independent queries and EVERY one of them is scored against every document (out [q_batch, B])
-static int score_padded(const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask,
-                        int32_t B, int32_t Ld, int32_t dim, float* out, float* colmax_out, flmr_stream_t stream, bool cross = false) {
+// the padded scorer's form: the fp16-split MFMA kernel for dim == 128 unless FLMR_SCORE_IMPL=valu asks for the plain-FMA one
+enum class score_form : uint8_t { mfma, valu };
+static int score_form_of(int32_t dim, score_form* form) {
+    flmr_options opt;
+    RUN(flmr_process_options(&opt));
+    *form = (dim == FLMR_DIM && !opt.score_valu) ? score_form::mfma : score_form::valu;
+    return FLMR_OK;
+}
+
+static int score_padded_form(score_form form, const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask,
+                             int32_t B, int32_t Ld, int32_t dim, float* out, float* colmax_out, flmr_stream_t stream, bool cross) {
     if (!Q || !D || !mask || (!out && !colmax_out)) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     if (!cross && q_batch != 1 && q_batch != B) FLMR_FAIL(FLMR_ERR_INVALID, "q_batch must be 1 or B");
     if (cross && (q_batch < 1 || q_batch > 65535)) FLMR_FAIL(FLMR_ERR_INVALID, "cross scoring takes 1..65535 queries per call");
@@ -440,7 +451,8 @@ static int score_padded(const float* Q, int32_t q_batch, int32_t nq, const float
     if (cross && q_batch == 1) cross = false;   // (the broadcast form)
     if ((size_t)nq * 4 > 48 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dim == FLMR_DIM && !flmr_opts().is(FLMR_OPT_SCORE_IMPL, "valu")) {
+    if (form == score_form::mfma) {
+        if (dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the MFMA scorer needs dim == %d", FLMR_DIM);
         scratch sc;
         const int nqp = (int)flmr_round_up(nq, 32);
         _Float16 *qh, *ql;
@@ -460,6 +472,13 @@ static int score_padded(const float* Q, int32_t q_batch, int32_t nq, const float
                        out, colmax_out);
     FLMR_LAUNCH_CHECK();
     return FLMR_OK;
+}
+
+static int score_padded(const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask,
+                        int32_t B, int32_t Ld, int32_t dim, float* out, float* colmax_out, flmr_stream_t stream, bool cross = false) {
+    score_form form;
+    RUN(score_form_of(dim, &form));
+    return score_padded_form(form, Q, q_batch, nq, D, mask, B, Ld, dim, out, colmax_out, stream, cross);
 }
 
 extern "C" int flmr_colbert_score_padded(const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask,

@@ -13,6 +13,27 @@ extern "C" const char* flmr_stage_name(int32_t s) { return (s >= 0 && s < FLMR_N
 
 #define FLMR_PROF_RING 8
 
+// ---- the batch plan: which kernel form runs at every stage (flmr_plan_batch below) --------------------------------------------
+enum class s2_form : uint8_t { gather_f32, gather, xcd, walk, xcda };   // xcda: hi-only pass on the sliced kernel, band rescored by the gather
+struct flmr_plan {
+    bool sparse;            // compact score rows of the surviving centroids (fp16-split stage 0, one column tile) instead of the whole table
+    flmr_s0_choice s0;      // stage-0 kernel and its partial-list geometry
+    bool hi_first;          // stage 0 writes the "hi first" bounds q_err / q_err_sum
+    bool chunked;           // candidates by the chunked kernel (else FLMR_CAND_IMPL=atomic)
+    bool hits;              // hit prefilter
+    bool scatter;           // stage 1 by list scatter for the queries it takes (hit_valid)
+    bool fast;              // cand_plan_kernel plans the fast forms (and decides the dense modes); else the slot form
+    int32_t img_rows;       // score-row images of the dense image form (0: it does not run)
+    bool dense, exact_too;  // the dense stage-1 forms run; the exact form also takes the queries beyond the images
+    bool qualifying;        // qualifying_kernel runs: nqual, row_ovf and the compact rows are this batch's
+    bool recompute;         // the recompute form for queries over the score-row capacity
+    bool modes;             // s1_dense_modes_kernel runs (mode / scan_skip needed and not made by cand_plan_kernel)
+    bool scan;              // the code-scanning stage 1 runs for the queries no other form took
+    s2_form s2;
+    s2_sw s2_gather;        // the row-gather kernel's form
+    s3_form s3;
+};
+
 struct flmr_searcher {
     const flmr_index* ix;
     int32_t max_queries, max_nq;
@@ -49,11 +70,10 @@ struct flmr_searcher {
     int32_t s1d_img_rows;       // score-row images the LDS form holds (0: no dense form on this index)
     int32_t* cand_fast;         // flmr_cand_args::fast_state ([FLMR_FAST_HDR + 2 * max_queries]; the header words live as long as the searcher)
     // last call (for taps)
-    int32_t last_nqueries, last_ncol, last_ndocs, last_full_table;
+    int32_t last_nqueries, last_ncol, last_ndocs;
+    flmr_plan last_plan;        // what the last call ran
     flmr_cand_args last_ca{};   // candidate-stage arguments of the last batch (lazy FLMR_TAP_CANDIDATES in scatter mode)
-    bool last_scatter = false;
-    bool last_dense = false;    // the last batch ran the dense stage-1 forms for the queries the list-scatter forms left
-    bool last_hi_first = false; // the last batch's stage 0 wrote q_err / q_err_sum (FLMR_TAP_Q_ERR*)
+    bool last_cand_lazy;        // the last batch's list-scatter forms skipped the ascending candidate lists (built on FLMR_TAP_CANDIDATES)
     hipStream_t last_stream;
     bool profiling;
     bool full_table;  // keep the whole centroid-score table (needed by the CENTROID_SCORES tap / retrieve())
@@ -91,11 +111,14 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
     int rc = check_params(maxp);
     if (rc) return rc;
     if (max_queries < 1 || max_nq < 1) FLMR_FAIL(FLMR_ERR_INVALID, "max_queries/max_nq must be >= 1");
+    flmr_options opt;
+    rc = flmr_process_options(&opt);
+    if (rc) return rc;
     flmr_searcher* s = new (std::nothrow) flmr_searcher();
     if (!s) FLMR_FAIL(FLMR_ERR_NOMEM, "host allocation failed");
     memset(s, 0, sizeof(*s));
     s->ix = ix; s->max_queries = max_queries; s->max_nq = max_nq; s->maxp = *maxp;
-    s->opt = flmr_process_options();
+    s->opt = opt;
     const int nqc = maxp->nq_cand < max_nq ? maxp->nq_cand : max_nq;
     s->ncol_max = (int32_t)flmr_round_up(nqc, 32);
     s->idx_words = (int32_t)flmr_ceil_div(ix->K, 32);
@@ -118,11 +141,8 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
     // rows of each query's surviving centroids, at most row_cap of them (2 MB per query at the default).
     s->cs = nullptr;
     {
-        const char* rc_opt = s->opt.has(FLMR_OPT_ROW_CAP) ? s->opt.v[FLMR_OPT_ROW_CAP] : nullptr;
-        long cap = rc_opt ? atol(rc_opt) : 16384;
-        if (cap < 64) cap = 64;
-        if (cap > 65535) cap = 65535;   // (the code-scanning stage 1 keeps 16-bit ranks in LDS)
-        s->row_cap = (int32_t)(cap < ix->K ? cap : ix->K);
+        const int32_t cap = s->opt.row_cap ? s->opt.row_cap : 16384;   // (at most 65535: the code-scanning stage 1 keeps 16-bit ranks in LDS)
+        s->row_cap = cap < ix->K ? cap : ix->K;
     }
     WS(rows, B * (size_t)s->row_cap * 32);
     WS(idx_prefix, B * (size_t)s->idx_words);
@@ -158,7 +178,7 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
     WS(key_count, B);
     WS(s1_slot, B * (size_t)nd);
     WS(s2_slot, B * (size_t)nd4);
-    if (ix->doc_splits && s->ncol_max == 32 && (flmr_stage2_xcd_pays(ix) || s->opt.is(FLMR_OPT_S2_IMPL, "xcd"))) {
+    if (ix->doc_splits && s->ncol_max == 32 && (flmr_stage2_xcd_pays(ix) || s->opt.s2 == s2_sw::xcd)) {
         // optional: without it (1 KB per query and survivor; e.g. out of memory) stage 2 runs in its gather form
         const size_t bytes = flmr_stage2_xcd_part_floats(ix, (int64_t)B, nd) * sizeof(float);
         if (hipMalloc(reinterpret_cast<void**>(&s->s2_part), bytes) == hipSuccess) s->bytes += (int64_t)bytes;
@@ -171,7 +191,7 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
     WS(chunk_hits, B * (size_t)ix->nchunks);
     WS(cand_hit, B * (size_t)s->cand_cap);
     // dense stage 1: needs the sorted code copy (whole 16-byte pieces are read: its padding) and 32-bit token offsets
-    s->s1d_img_rows = (ix->codes_sorted && s->ncol_max == 32 && !s->opt.is(FLMR_OPT_S1_IMPL, "scan")) ? flmr_s1_dense_image_rows(max_queries, s->idx_words, ix->mean_ulen) : 0;
+    s->s1d_img_rows = (ix->codes_sorted && s->ncol_max == 32 && s->opt.s1 != s1_sw::scan) ? flmr_s1_dense_image_rows(max_queries, s->idx_words, ix->mean_ulen) : 0;
     WS(s1d_any, 16); WS(s1d_mode, B); WS(s1d_band_count, B); WS(s1d_err, B); WS(s1d_in_count, B); WS(s1d_scan_skip, B); WS(row_ovf, B);
     if (s->s1d_img_rows > 0) WS(s1d_band, B * (size_t)s->cand_cap);
     WS(q3_hi, B * (size_t)flmr_round_up(max_nq, 32) * FLMR_DIM);
@@ -320,8 +340,6 @@ extern "C" int flmr_searcher_stage_ms(flmr_searcher_t* s, float* ms) {
 
 // ---- one batch = a context (validated parameters + kernel argument blocks) run through stage helpers -----------------
 struct run_ctx {
-    flmr_opt_scope scope;   // every launch of this call sees the searcher's switch snapshot
-    explicit run_ctx(flmr_searcher* s_) : scope(s_ ? &s_->opt : nullptr) {}
     flmr_searcher* s;
     const float* Q;
     const int32_t* q_lens;
@@ -331,6 +349,7 @@ struct run_ctx {
     hipStream_t st;
     flmr_s0_args a0{};
     flmr_filter_args f{};
+    flmr_plan plan;
     int stage;  // profiling event cursor
     int ev_set; // event set of this call
 };
@@ -407,9 +426,8 @@ __global__ void sanitize_q_lens_kernel(const int32_t* in, int32_t n, int32_t nq,
 static bool sparse_path(const flmr_searcher* s, int ncol) {
     const flmr_index* ix = s->ix;
     const flmr_options& o = s->opt;
-    const bool f16_path = ix->centroids_f16_exact && ix->centroids_f16 && (ix->K % 64 == 0) &&
-                          !(o.has(FLMR_OPT_S0_IMPL) && !o.is(FLMR_OPT_S0_IMPL, "f16") && !o.is(FLMR_OPT_S0_IMPL, "f16rs") && !o.is(FLMR_OPT_S0_IMPL, "qs1"));
-    return f16_path && ncol == 32 && !s->full_table && !o.has(FLMR_OPT_FULL_TABLE);
+    const bool f16_path = ix->centroids_f16_exact && ix->centroids_f16 && (ix->K % 64 == 0) && o.s0 != s0_sw::f32 && o.s0 != s0_sw::valu;
+    return f16_path && ncol == 32 && !s->full_table && !o.full_table;
 }
 
 extern "C" int flmr_searcher_probe_supported(const flmr_searcher_t* s, int32_t nq, const flmr_search_params_t* p,
@@ -420,10 +438,75 @@ extern "C" int flmr_searcher_probe_supported(const flmr_searcher_t* s, int32_t n
     return FLMR_OK;
 }
 
-static inline bool f16num_early(const flmr_searcher* s) { return s->numerics == FLMR_NUMERICS_GPU_FP16; }
+// the stage-3 arguments of a call (`s0_images`: stage 0 of THIS call split the same queries -- flmr_search_batch, not the phases)
+static flmr_maxsim_args s3_args(const run_ctx& c, bool s0_images) {
+    flmr_searcher* s = c.s;
+    flmr_maxsim_args m{};
+    m.ix = s->ix; m.Q = c.Q; m.q_lens = c.q_lens; m.nqueries = c.nqueries; m.nq = c.nq;
+    m.pids = s->s2_pids; m.pid_stride = s->maxp.ndocs / 4; m.counts = s->s2_count; m.max_count = c.p.ndocs / 4;
+    m.keys = s->keys3; m.key_stride = s->maxp.ndocs / 4; m.scores = s->doc_scores;
+    m.q_hi = s->q3_hi; m.q_lo = s->q3_lo;
+    m.gpu_fp16 = c.f.f16_round;
+    m.plan_desc = s->s3_desc; m.plan_stride = s->s3_desc_stride; m.plan_wbeg = s->s3_wbeg; m.plan_wcap = s->s3_wcap;
+    m.colmax_ws = s->s3_colmax; m.colmax_cap = s->s3_colmax_cap;
+    // Stage 0's fp16 images ARE stage 3's when every query row is a candidate-generation column (nq <= 32 <= nq_cand): rows
+    // below min(q_len, nq) real, the rest zero, one tile of 32 -- no second split launch
+    if (s0_images && c.sparse && !c.f.f16_round && c.nq <= 32 && c.nqc == c.nq && c.ncol == 32) {
+        m.q_hi = s->q_hi; m.q_lo = s->q_lo;
+        m.q_split_done = 1;
+    }
+    return m;
+}
+
+// The plan of one call: every stage's kernel form, from the searcher's switch snapshot, the index, the workspace and the batch.
+// `whole_batch`: flmr_search_batch.  Phase 2 of the sharded protocol scores only this shard's members (a fraction of ndocs per
+// query): the table walk, whose cost does not shrink with the number of survivors, is then the wrong form unless forced; so is the
+// XCD-sliced kernel, whose waves each take one eighth of 64 survivors' tokens (per-rank compute of a step at 8 shards,
+// profiles/shard_step_model.py: 2.16 ms sliced, 1.92 ms gather).  Also applies the stage-0 geometry to c.a0.
+static void plan_batch(run_ctx& c, bool whole_batch) {
+    flmr_searcher* s = c.s;
+    const flmr_index* ix = s->ix;
+    const flmr_options& o = s->opt;
+    flmr_plan& pl = c.plan;
+    pl = flmr_plan{};
+    pl.sparse = c.sparse;
+    // stage 0 (the block maxima of the row-stationary kernels are the full values: s0_select_cells must not assume otherwise)
+    pl.s0 = flmr_s0_choose(c.a0, o);
+    c.a0.nblk = pl.s0.nblk; c.a0.part_rows = pl.s0.part_rows; c.a0.grp_blocks = pl.s0.grp_blocks;
+    if (pl.s0.form == s0_form::f16_sparse || pl.s0.form == s0_form::f16_table) { c.a0.q_err = nullptr; c.a0.q_err_buf = nullptr; }
+    pl.hi_first = (pl.s0.form == s0_form::qs || pl.s0.form == s0_form::qs2) && c.a0.q_err_buf != nullptr;
+    // stage 1: the list scatter (single column tile, sparse or full table alike) for the queries it takes; the dense forms of
+    // flmr_stage1_dense.hip (sparse path, one column tile, CPU-path numerics) for those it leaves; the recompute form for queries over
+    // the score-row capacity; the code-scanning kernel for the rest (every query under FLMR_S1_IMPL=scan)
+    pl.chunked = !o.cand_atomic;
+    pl.hits = !o.s1_no_hitmap;
+    pl.scatter = pl.chunked && pl.hits && c.ncol == 32 && o.s1 != s1_sw::scan;
+    pl.fast = pl.scatter && o.s1 != s1_sw::slots;
+    pl.dense = s->s1d_img_rows > 0 && pl.chunked && c.sparse && c.ncol == 32 && !c.f.f16_round && o.s1 != s1_sw::scan;
+    pl.img_rows = pl.dense ? s->s1d_img_rows : 0;
+    pl.exact_too = pl.dense && o.s1 != s1_sw::image;   // (development: "image" leaves the queries beyond the images to the scan)
+    pl.qualifying = pl.chunked || c.sparse;
+    pl.recompute = c.sparse && s->row_cap < ix->K;
+    pl.scan = !(pl.dense && pl.exact_too);   // (with both dense forms on, every query the list scatter leaves is theirs or the recompute form's)
+    pl.modes = !pl.fast && (pl.dense || pl.scatter || pl.recompute);   // (else the scan takes every query: no skip list)
+    // stage 2
+    const bool walk_pays = ix->codes_sorted && ix->centroids_f16_tiled && flmr_stage2_walk_pays(ix, c.nqueries, c.p.ndocs);
+    const bool dflt = o.s2 == s2_sw::dflt;
+    const bool walk = c.sparse && !c.f.f16_round && ix->codes_sorted && ix->centroids_f16_tiled &&
+                      (o.s2 == s2_sw::walk || (dflt && whole_batch && walk_pays));
+    const bool xcd = !walk && c.sparse && s->s2_part && c.f.ncol == 32 && (o.s2 == s2_sw::xcd || (dflt && whole_batch && flmr_stage2_xcd_pays(ix)));
+    pl.s2 = xcd ? s2_form::xcd : walk ? s2_form::walk : c.sparse ? s2_form::gather : s2_form::gather_f32;
+    // default on the sliced kernel (the batch's error bounds at hand): hi-only pass, plan, full rescoring of the band by the gather
+    // kernel, finish (flmr_filter.hip) -- the same SET as the sorted form; any other FLMR_S2_IMPL keeps the full scores and the sorted list
+    if (whole_batch && pl.hi_first && s->s2_part && (o.s2 == s2_sw::xcda || (dflt && flmr_stage2_xcd_pays(ix) && !walk_pays)))
+        pl.s2 = s2_form::xcda;
+    pl.s2_gather = (o.s2 == s2_sw::regs || o.s2 == s2_sw::ldsb) ? o.s2 : s2_sw::lds;
+    // stage 3
+    pl.s3 = flmr_s3_choose(s3_args(c, whole_batch), o);
+}
 
 static int prepare_ctx(run_ctx& c, flmr_searcher* s, const float* Q, const int32_t* q_lens, int32_t nqueries, int32_t nq,
-                       const flmr_search_params_t* p, flmr_stream_t stream) {
+                       const flmr_search_params_t* p, flmr_stream_t stream, bool whole_batch = false) {
     if (!s || !Q) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     RUN(check_params(p));
     RUN(poll_status(s, false));
@@ -462,7 +545,7 @@ static int prepare_ctx(run_ctx& c, flmr_searcher* s, const float* Q, const int32
         }
         s->bytes += (int64_t)bytes;
     }
-    if (s->opt.has(FLMR_OPT_POISON)) {   // test runs: nothing may be read from an earlier batch's workspace
+    if (s->opt.poison) {   // test runs: nothing may be read from an earlier batch's workspace
         FLMR_HIP(hipMemsetAsync(s->rows, 0xFF, (size_t)nqueries * s->row_cap * 32 * sizeof(float), c.st));
         FLMR_HIP(hipMemsetAsync(s->idx_prefix, 0xFF, (size_t)nqueries * s->idx_words * sizeof(uint32_t), c.st));
         FLMR_HIP(hipMemsetAsync(s->qual, 0xFF, (size_t)nqueries * s->qmax * sizeof(int32_t), c.st));
@@ -471,22 +554,21 @@ static int prepare_ctx(run_ctx& c, flmr_searcher* s, const float* Q, const int32
         FLMR_HIP(hipMemsetAsync(s->keys3, 0xFF, (size_t)nqueries * (s->maxp.ndocs / 4) * sizeof(uint64_t), c.st));
     }
     a0.cs = c.sparse ? nullptr : s->cs; a0.idx_bits = s->idx_bits; a0.idx_words = s->idx_words;
-    a0.part_val = s->part_val; a0.part_idx = s->part_idx; a0.nblk = s->nblk;
+    a0.part_val = s->part_val; a0.part_idx = s->part_idx;
     a0.cells = s->cells; a0.ncell = s->ncell; a0.max_cells = s->max_cells;
     a0.q_hi = s->q_hi; a0.q_lo = s->q_lo; a0.centroids_f16_exact = ix->centroids_f16_exact;
     // "hi first" stage 0: on unless the fp16 numerics mode makes it moot (q_lo = 0) or FLMR_S0_IMPL asks for another kernel
-    a0.q_err_buf = f16num_early(s) ? nullptr : s->q_err;
+    a0.q_err_buf = f16num ? nullptr : s->q_err;
     // (any batch size since the cell selection reads the coarse level of maxima this path leaves: a single-query call takes 0.309 ms
     // with it, 0.322 ms with both products everywhere; before the coarse level the selection's serial pass over a near-tie column
     // -- most queries have one -- made the shortcut a loss under 16 queries)
 #ifndef S0_HIFIRST_MIN_QUERIES
 #define S0_HIFIRST_MIN_QUERIES 1
 #endif
-    a0.q_err = (!f16num_early(s) && (!s->opt.has(FLMR_OPT_S0_IMPL) || s->opt.is(FLMR_OPT_S0_IMPL, "qs1")) && nqueries >= S0_HIFIRST_MIN_QUERIES) ? s->q_err : nullptr;
+    a0.q_err = (!f16num && (s->opt.s0 == s0_sw::dflt || s->opt.s0 == s0_sw::qs1) && nqueries >= S0_HIFIRST_MIN_QUERIES) ? s->q_err : nullptr;
     a0.q_err_sum = s->q_err_sum;
     a0.cen_norm_max = ix->cen_norm_max;
     a0.centroids_f16 = ix->centroids_f16;
-    a0.part_rows = 0;
     a0.full_table = c.sparse ? 0 : 1;
     flmr_filter_args& f = c.f;
     f.cs = c.sparse ? s->rows : s->cs; f.cs_query_stride = c.sparse ? (int64_t)s->row_cap * 32 : (int64_t)ix->K * ncol;
@@ -495,9 +577,9 @@ static int prepare_ctx(run_ctx& c, flmr_searcher* s, const float* Q, const int32
     f.nqueries = nqueries; f.q_lens = q_lens; f.codes = ix->codes; f.doclens = nullptr; f.offsets = ix->doc_offsets;
     f.f16_round = f16num ? 1 : 0;
     f.ulen_sorted = ix->doc_ulen;
+    plan_batch(c, whole_batch);
     s->last_nqueries = nqueries; s->last_ncol = ncol; s->last_ndocs = p->ndocs; s->last_stream = c.st;
-    s->last_full_table = a0.full_table;
-    s->last_hi_first = c.sparse && a0.q_err_buf != nullptr && (int64_t)ix->K * 256 < (1ll << 32) && !s->opt.is(FLMR_OPT_S0_IMPL, "f16rs");
+    s->last_plan = c.plan;
     return FLMR_OK;
 }
 
@@ -507,7 +589,7 @@ static int stage_cand_s1(run_ctx& c, uint64_t* out_keys);
 static int stage_s0_s1(run_ctx& c, uint64_t* out_keys) {
     hipStream_t st = c.st;
     RUN(mark(c));
-    RUN(flmr_launch_centroid_scores(c.a0, st));
+    RUN(flmr_launch_centroid_scores(c.a0, c.plan.s0.form, st));
     RUN(mark(c));
     RUN(flmr_launch_select_cells(c.a0, st));
     RUN(mark(c));
@@ -518,17 +600,9 @@ static int stage_s0_s1(run_ctx& c, uint64_t* out_keys) {
 static int stage_cand_s1(run_ctx& c, uint64_t* out_keys) {
     flmr_searcher* s = c.s;
     const flmr_index* ix = s->ix;
+    const flmr_plan& pl = c.plan;
     hipStream_t st = c.st;
-    // FLMR_CAND_IMPL=atomic keeps the first implementation (global atomicOr bitmap + separate hit bitmap) for A/B runs
-    const bool chunked = !s->opt.is(FLMR_OPT_CAND_IMPL, "atomic");
-    const bool use_hits = !s->opt.has(FLMR_OPT_S1_NO_HITMAP);
-    bool scatter = false;
-    s->last_scatter = false;
-    // the dense stage-1 forms (flmr_stage1_dense.hip) need the sparse path, one column tile and the CPU-path numerics
-    const bool dense = s->s1d_img_rows > 0 && chunked && c.sparse && c.ncol == 32 && !c.f.f16_round && !s->opt.is(FLMR_OPT_S1_IMPL, "scan");
-    s->last_dense = dense;
     const int32_t* sel_counts = s->cand_count;
-    bool modes_fused = false;
     flmr_cand_args ca{};
     {
         ca.nqueries = c.nqueries; ca.idx_words = s->idx_words; ca.max_cells = s->max_cells; ca.qmax = s->qmax;
@@ -538,39 +612,36 @@ static int stage_cand_s1(run_ctx& c, uint64_t* out_keys) {
         ca.qual = s->qual; ca.nqual = s->nqual; ca.hit_valid = s->hit_valid;
         ca.cand_bits = s->bitmap; ca.hit_bits = s->hit_bits; ca.chunk_cnt = s->chunk_cnt;
         ca.cand = s->cand; ca.cand_hit = s->cand_hit; ca.cand_count = s->cand_count; ca.overflow = s->overflow;
-        // stage 1 by scatter over the surviving centroids' IVF lists (single column tile, sparse or full table alike);
-        // FLMR_S1_IMPL=scan keeps the code-scanning kernel for every query (A/B runs, cross-check tests)
-        scatter = chunked && use_hits && c.ncol == 32 && !s->opt.is(FLMR_OPT_S1_IMPL, "scan");
-        ca.scatter = scatter ? 1 : 0;
-        modes_fused = scatter && !s->opt.is(FLMR_OPT_S1_IMPL, "slots");   // (cand_plan_kernel runs)
+        ca.scatter = pl.scatter ? 1 : 0;
         ca.cs = c.f.cs; ca.cs_query_stride = c.f.cs_query_stride; ca.nq_cand = c.nqc; ca.q_lens = c.q_lens;
         ca.cs_compact = c.f.cs_compact; ca.idx_prefix = s->idx_prefix;
         ca.rows_out = c.sparse ? s->rows : nullptr; ca.cen16 = ix->centroids_f16; ca.q_hi = s->q_hi; ca.q_lo = s->q_lo;
         ca.keys = s->keys1; ca.key_count = s->key_count; ca.chunk_hits = s->chunk_hits; ca.n_select = c.p.ndocs;
         ca.f16_round = c.f.f16_round;
-        ca.fast_state = s->opt.is(FLMR_OPT_S1_IMPL, "slots") ? nullptr : s->cand_fast;
+        ca.fast_state = s->opt.s1 == s1_sw::slots ? nullptr : s->cand_fast;
         ca.row_ovf = s->row_ovf;
         // who takes which query afterwards: the list-scatter forms (hit_valid), the dense forms, the recompute form (row_ovf), the scan
         // (the rest); decided per query by cand_plan_kernel when it runs, else by flmr_launch_s1_dense_modes below
-        if (modes_fused) {
+        if (pl.fast) {
             ca.s1d_mode = s->s1d_mode; ca.s1d_scan_skip = s->s1d_scan_skip; ca.s1d_any = s->s1d_any;
-            ca.s1d_img_rows = dense ? s->s1d_img_rows : 0;
-            ca.s1d_exact_too = (dense && !s->opt.is(FLMR_OPT_S1_IMPL, "image")) ? 1 : 0;
+            ca.s1d_img_rows = pl.img_rows;
+            ca.s1d_exact_too = pl.exact_too ? 1 : 0;
         }
     }
-    if (chunked) {
+    if (pl.chunked) {
         RUN(flmr_launch_candidates_chunked(ca, st));
-        s->last_ca = ca; s->last_scatter = scatter;
+        s->last_ca = ca; s->last_cand_lazy = pl.scatter;
         RUN(mark(c));
         RUN(mark(c));  // (the hit set is produced by the same pass: the s1_hitmap stage is empty in this mode)
     } else {
-        if (c.sparse) RUN(flmr_launch_qualifying(ca, st));   // (the compact score rows stage 1 reads)
+        if (pl.qualifying) RUN(flmr_launch_qualifying(ca, st));   // (the compact score rows stage 1 reads)
         RUN(flmr_launch_ivf_mark(s->cells, s->ncell, s->max_cells, c.nqueries, ix->ivf_pids, ix->ivf_offsets, s->bitmap,
                                  s->bitmap_words, st));
         RUN(flmr_launch_compact(s->bitmap, s->bitmap_words, ix->num_passages, c.nqueries, s->cand, s->cand_cap,
                                 s->cand_count, s->overflow, st));
+        s->last_cand_lazy = false;
         RUN(mark(c));
-        if (use_hits)
+        if (pl.hits)
             RUN(flmr_launch_hit_bitmap(s->idx_bits, s->idx_words, c.nqueries, ix->ivf_pids, ix->ivf_offsets, s->cand_count,
                                        s->hit_bits, s->bitmap_words, s->hit_valid, st));
         RUN(mark(c));
@@ -579,12 +650,11 @@ static int stage_cand_s1(run_ctx& c, uint64_t* out_keys) {
     // the dense forms of flmr_stage1_dense.hip -- fp16 images of the query's score rows in LDS, upper-bound keys for every
     // candidate, the band around the cut rescored exactly -- where the rows fit (<= ~2 k survivors), the same kernel's exact form
     // beyond; the round-5 scan keeps the cases those do not cover (several column tiles, the fp16 numerics mode, no sorted copy).
-    const bool exact_too = dense && !s->opt.is(FLMR_OPT_S1_IMPL, "image");   // (development: "image" leaves the queries beyond the images to the scan)
-    if (!modes_fused)
-        RUN(flmr_launch_s1_dense_modes(scatter ? s->hit_valid : nullptr, s->nqual, s->row_ovf, c.nqueries, dense ? s->s1d_img_rows : 0,
-                                       exact_too ? 1 : 0, s->s1d_mode, s->s1d_scan_skip, s->s1d_any, st));
-    const int32_t* scan_skip = s->s1d_scan_skip;
-    if (dense) {
+    if (pl.modes)
+        RUN(flmr_launch_s1_dense_modes(pl.scatter ? s->hit_valid : nullptr, pl.qualifying ? s->nqual : nullptr,
+                                       pl.qualifying ? s->row_ovf : nullptr, c.nqueries, pl.img_rows, pl.exact_too ? 1 : 0,
+                                       s->s1d_mode, s->s1d_scan_skip, s->s1d_any, st));
+    if (pl.dense) {
         flmr_s1d_args d{};
         d.codes = ix->codes_sorted; d.offsets = ix->doc_offsets; d.ulen = ix->doc_ulen; d.codes_len = ix->N;
         d.idx_bits = s->idx_bits; d.idx_prefix = s->idx_prefix; d.idx_words = s->idx_words;
@@ -601,13 +671,13 @@ static int stage_cand_s1(run_ctx& c, uint64_t* out_keys) {
         RUN(flmr_launch_s1_exact(d, ix->mean_ulen, st));
         sel_counts = s->s1d_in_count;
     }
-    if (c.sparse && s->row_cap < ix->K)   // (a query over the score-row capacity; leaves at once when there is none)
+    if (pl.recompute)   // (a query over the score-row capacity; leaves at once when there is none)
         RUN(flmr_launch_filter_stage1_recompute(c.f, s->idx_bits, s->idx_words, s->cand, s->cand_cap, s->cand_count, s->row_ovf, s->keys1,
                                                 ix->centroids_f16, s->q_hi, s->q_lo, st));
-    if (!(dense && exact_too))   // (with both dense forms on, every query the list scatter leaves is theirs or the recompute form's: nothing to scan)
+    if (pl.scan)
         RUN(flmr_launch_filter_stage1(c.f, s->idx_bits, s->idx_words, s->cand, s->cand_cap, s->cand_count, s->keys1,
-                                      (use_hits && !chunked) ? s->hit_bits : nullptr, s->bitmap_words, use_hits ? s->hit_valid : nullptr,
-                                      (use_hits && chunked) ? s->cand_hit : nullptr, st, scan_skip));
+                                      (pl.hits && !pl.chunked) ? s->hit_bits : nullptr, s->bitmap_words, pl.hits ? s->hit_valid : nullptr,
+                                      (pl.hits && pl.chunked) ? s->cand_hit : nullptr, st, (pl.modes || pl.fast) ? s->s1d_scan_skip : nullptr));
     RUN(mark(c));
     RUN(flmr_launch_select_topn(s->keys1, s->cand_cap, sel_counts, c.nqueries, c.p.ndocs, s->s1_pids, s->maxp.ndocs,
                                 s->s1_count, st, out_keys, (uint64_t)ix->pid_base));
@@ -615,50 +685,34 @@ static int stage_cand_s1(run_ctx& c, uint64_t* out_keys) {
     return push_status(c);
 }
 
-// S2 over s->s1_pids / s1_count -> s->keys2 (slot-aligned with s1_pids)
-// `whole_batch`: the survivors are the full top-ndocs lists of a single-index search (flmr_search_batch).  Phase 2 of the
-// sharded protocol scores only this shard's members (a fraction of ndocs per query): the table walk, whose cost does not
-// shrink with the number of survivors, is then the wrong form unless forced; so is the XCD-sliced kernel, whose waves each take
-// one eighth of 64 survivors' tokens (per-rank compute of a step at 8 shards, profiles/shard_step_model.py: 2.16 ms sliced,
-// 1.92 ms gather).
-static int stage_s2(run_ctx& c, bool whole_batch) {
+// S2 over s->s1_pids / s1_count -> s->keys2 (slot-aligned with s1_pids), in the full-score form of the plan
+static int stage_s2(run_ctx& c) {
     flmr_searcher* s = c.s;
     const flmr_index* ix = s->ix;
-    const flmr_options& o = s->opt;
-    const bool walk = c.sparse && !c.f.f16_round && ix->codes_sorted && ix->centroids_f16_tiled &&
-                      (o.is(FLMR_OPT_S2_IMPL, "walk") ||
-                       (!o.has(FLMR_OPT_S2_IMPL) && whole_batch && flmr_stage2_walk_pays(ix, c.nqueries, c.p.ndocs)));
-    const bool xcd = !walk && c.sparse && s->s2_part && c.f.ncol == 32 &&
-                     (o.is(FLMR_OPT_S2_IMPL, "xcd") || (!o.has(FLMR_OPT_S2_IMPL) && whole_batch && flmr_stage2_xcd_pays(ix)));
-    if (xcd)
-        RUN(flmr_launch_filter_stage2_xcd(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs, ix,
-                                          s->q_hi, s->q_lo, s->s2_part, s->maxp.ndocs, c.st));
-    else if (walk)
-        RUN(flmr_launch_filter_stage2_walk(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs,
-                                           ix->centroids_f16_tiled, s->q_hi, s->q_lo, ix->codes_sorted, c.st));
-    else if (c.sparse)
-        RUN(flmr_launch_filter_stage2_mfma(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs,
-                                           ix->centroids_f16, s->q_hi, s->q_lo, c.st));
-    else
-        RUN(flmr_launch_filter_stage2(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs, c.st));
-    return FLMR_OK;
+    switch (c.plan.s2) {
+        case s2_form::xcd:
+            return flmr_launch_filter_stage2_xcd(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs, ix,
+                                                 s->q_hi, s->q_lo, s->s2_part, s->maxp.ndocs, c.st);
+        case s2_form::walk:
+            return flmr_launch_filter_stage2_walk(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs,
+                                                  ix->centroids_f16_tiled, s->q_hi, s->q_lo, ix->codes_sorted, c.st);
+        case s2_form::gather:
+            return flmr_launch_filter_stage2_mfma(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs,
+                                                  ix->centroids_f16, s->q_hi, s->q_lo, c.plan.s2_gather, c.st);
+        case s2_form::gather_f32:
+            return flmr_launch_filter_stage2(c.f, s->s1_pids, s->maxp.ndocs, s->s1_count, c.p.ndocs, s->keys2, s->maxp.ndocs, c.st);
+        default: FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the approximate-then-refine stage 2 runs for whole batches only");
+    }
 }
 
-// S2 of a whole batch + the selection of the ndocs/4 survivors -> s->s2_pids / s2_count.
-// Default on the sliced kernel (sparse path, CPU-path numerics, the batch's error bounds at hand): hi-only pass, plan, full
-// rescoring of the band by the gather kernel, finish (flmr_filter.hip) -- the same SET as the sorted form.  FLMR_S2_IMPL set to
-// anything but "xcda" keeps the full-score forms and the sorted list (taps, cross-check tests).
+// S2 of a whole batch + the selection of the ndocs/4 survivors -> s->s2_pids / s2_count (in (score,pid) order, or -- approximate-
+// then-refine -- as the same set)
 static int stage_s2_select(run_ctx& c) {
     flmr_searcher* s = c.s;
     const flmr_index* ix = s->ix;
-    const flmr_options& o = s->opt;
     const int nd4m = s->maxp.ndocs / 4;
-    const bool bounds = c.sparse && !c.f.f16_round && c.a0.q_err_buf != nullptr && c.f.ncol == 32 &&
-                        c.a0.centroids_f16 && (int64_t)ix->K * 256 < (1ll << 32) && !o.is(FLMR_OPT_S0_IMPL, "f16rs");
-    const bool approx = bounds && s->s2_part && (o.is(FLMR_OPT_S2_IMPL, "xcda") || (!o.has(FLMR_OPT_S2_IMPL) && flmr_stage2_xcd_pays(ix) &&
-                        !(ix->codes_sorted && ix->centroids_f16_tiled && flmr_stage2_walk_pays(ix, c.nqueries, c.p.ndocs))));
-    if (!approx) {
-        RUN(stage_s2(c, true));
+    if (c.plan.s2 != s2_form::xcda) {
+        RUN(stage_s2(c));
         return flmr_launch_sort_topn(s->keys2, s->maxp.ndocs, s->s1_count, c.p.ndocs, c.nqueries, c.p.ndocs / 4, s->s2_pids,
                                      nullptr, nd4m, s->s2_count, 0, 0, c.st);
     }
@@ -667,38 +721,22 @@ static int stage_s2_select(run_ctx& c) {
     RUN(flmr_launch_s2_refine_plan(s->keys2, s->maxp.ndocs, s->s1_count, c.p.ndocs, c.nqueries, c.p.ndocs / 4, s->q_err_sum,
                                    s->s2_pids, nd4m, s->s2_band, s->maxp.ndocs, s->s2_band_count, s->s2_need, s->s2_def, c.st));
     RUN(flmr_launch_filter_stage2_mfma(c.f, s->s2_band, s->maxp.ndocs, s->s2_band_count, c.p.ndocs, s->keys2b, s->maxp.ndocs,
-                                       ix->centroids_f16, s->q_hi, s->q_lo, c.st));
+                                       ix->centroids_f16, s->q_hi, s->q_lo, s2_sw::lds, c.st));
     return flmr_launch_s2_refine_finish(s->keys2b, s->maxp.ndocs, s->s2_band_count, s->s2_need, s->s2_def, c.p.ndocs, c.nqueries,
                                         s->s2_pids, nd4m, s->s2_count, c.st);
 }
 
 // S3 over s->s2_pids / s2_count -> s->keys3 / doc_scores (slot-aligned with s2_pids)
-// `s0_images`: stage 0 of THIS call split the same queries (flmr_search_batch; not the phase entry points)
 static int stage_s3(run_ctx& c, bool s0_images) {
-    flmr_searcher* s = c.s;
-    flmr_maxsim_args m{};
-    m.ix = s->ix; m.Q = c.Q; m.q_lens = c.q_lens; m.nqueries = c.nqueries; m.nq = c.nq;
-    m.pids = s->s2_pids; m.pid_stride = s->maxp.ndocs / 4; m.counts = s->s2_count; m.max_count = c.p.ndocs / 4;
-    m.keys = s->keys3; m.key_stride = s->maxp.ndocs / 4; m.scores = s->doc_scores;
-    m.q_hi = s->q3_hi; m.q_lo = s->q3_lo;
-    m.gpu_fp16 = c.f.f16_round;
-    m.plan_desc = s->s3_desc; m.plan_stride = s->s3_desc_stride; m.plan_wbeg = s->s3_wbeg; m.plan_wcap = s->s3_wcap;
-    m.colmax_ws = s->s3_colmax; m.colmax_cap = s->s3_colmax_cap;
-    // Stage 0's fp16 images ARE stage 3's when every query row is a candidate-generation column (nq <= 32 <= nq_cand): rows
-    // below min(q_len, nq) real, the rest zero, one tile of 32 -- no second split launch
-    if (s0_images && c.sparse && !c.f.f16_round && c.nq <= 32 && c.nqc == c.nq && c.ncol == 32) {
-        m.q_hi = s->q_hi; m.q_lo = s->q_lo;
-        m.q_split_done = 1;
-    }
-    return flmr_launch_maxsim(m, c.st);
+    return flmr_launch_maxsim(s3_args(c, s0_images), c.plan.s3, c.st);
 }
 
 extern "C" int flmr_search_batch(flmr_searcher_t* s, const float* Q, const int32_t* q_lens, int32_t nqueries,
                                  int32_t nq, const flmr_search_params_t* p, int32_t* out_pids, float* out_scores,
                                  int32_t* out_counts, flmr_stream_t stream) {
     if (!out_pids || !out_scores || !out_counts) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    run_ctx c(s);
-    RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
+    run_ctx c;
+    RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream, true));
     RUN(stage_s0_s1(c, nullptr));
     // ---- S2: full centroid MaxSim over the survivors, keep ndocs/4 (in (score,pid) order, or -- approximate-then-refine --
     // as the same set) ----------------
@@ -723,7 +761,7 @@ extern "C" int flmr_search_batch(flmr_searcher_t* s, const float* Q, const int32
 extern "C" int flmr_search_phase1(flmr_searcher_t* s, const float* Q, const int32_t* q_lens, int32_t nqueries, int32_t nq,
                                   const flmr_search_params_t* p, uint64_t* out_keys, flmr_stream_t stream) {
     if (!out_keys) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    run_ctx c(s);
+    run_ctx c;
     RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
     if (s->maxp.ndocs != p->ndocs) FLMR_FAIL(FLMR_ERR_INVALID, "the phased protocol needs ndocs == the searcher's max ndocs (key rows are ndocs wide)");
     return stage_s0_s1(c, out_keys);
@@ -745,7 +783,7 @@ extern "C" int flmr_search_probe(flmr_searcher_t* s, const float* Q, const int32
                                  int32_t* out_cells, int32_t* out_ncell, flmr_stream_t stream) {
     if (q_count == 0 && s && q_begin >= 0 && q_begin <= nqueries) return FLMR_OK;  // an empty slice (more ranks than queries) has no outputs
     if (!out_idx_bits || !out_cells || !out_ncell) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    run_ctx c(s);
+    run_ctx c;
     RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
     if (!c.sparse) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "query-split stage 0 needs the sparse-table path (fp16-exact centroids, K %% 64 == 0, nq_cand <= 32)");
     if (q_begin < 0 || q_count < 0 || q_begin + q_count > nqueries) FLMR_FAIL(FLMR_ERR_INVALID, "query slice [%d, %d) outside the batch of %d", q_begin, q_begin + q_count, nqueries);
@@ -754,7 +792,7 @@ extern "C" int flmr_search_probe(flmr_searcher_t* s, const float* Q, const int32
     a0.q_lens = c.q_lens ? c.q_lens + q_begin : nullptr;
     a0.nqueries = q_count;
     a0.idx_bits = out_idx_bits; a0.cells = out_cells; a0.ncell = out_ncell;
-    RUN(flmr_launch_centroid_scores(a0, c.st));
+    RUN(flmr_launch_centroid_scores(a0, c.plan.s0.form, c.st));
     return flmr_launch_select_cells(a0, c.st);
 }
 
@@ -763,7 +801,7 @@ extern "C" int flmr_search_phase1_probed(flmr_searcher_t* s, const float* Q, con
                                          const int32_t* cells, const int32_t* ncell, uint64_t* out_keys,
                                          flmr_stream_t stream) {
     if (!idx_bits || !cells || !ncell || !out_keys) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    run_ctx c(s);
+    run_ctx c;
     RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
     if (!c.sparse) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "query-split stage 0 needs the sparse-table path (fp16-exact centroids, K %% 64 == 0, nq_cand <= 32)");
     if (s->maxp.ndocs != p->ndocs) FLMR_FAIL(FLMR_ERR_INVALID, "the phased protocol needs ndocs == the searcher's max ndocs (key rows are ndocs wide)");
@@ -784,12 +822,12 @@ extern "C" int flmr_search_phase2(flmr_searcher_t* s, const float* Q, const int3
                                   const flmr_search_params_t* p, const uint64_t* global_s1, int32_t n_in, uint64_t* out_keys,
                                   flmr_stream_t stream) {
     if (!global_s1 || !out_keys) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    run_ctx c(s);
+    run_ctx c;
     RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
     if (n_in > p->ndocs) FLMR_FAIL(FLMR_ERR_INVALID, "n_in=%d > ndocs=%d", n_in, p->ndocs);
     RUN(flmr_launch_filter_local_keys(global_s1, nqueries, n_in, s->ix->pid_base, s->ix->num_passages, s->s1_pids, s->maxp.ndocs,
                                       s->s1_count, c.st, s->s1_slot));
-    RUN(stage_s2(c, false));
+    RUN(stage_s2(c));
     return flmr_launch_export_keys_slotted(s->keys2, s->maxp.ndocs, s->s1_count, s->s1_slot, nqueries, (uint64_t)s->ix->pid_base,
                                            p->ndocs, out_keys, c.st);
 }
@@ -800,7 +838,7 @@ extern "C" int flmr_search_phase3(flmr_searcher_t* s, const float* Q, const int3
                                   const flmr_search_params_t* p, const uint64_t* global_s2, int32_t n_in, uint64_t* out_keys,
                                   flmr_stream_t stream) {
     if (!global_s2 || !out_keys) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    run_ctx c(s);
+    run_ctx c;
     RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
     if (n_in > p->ndocs / 4) FLMR_FAIL(FLMR_ERR_INVALID, "n_in=%d > ndocs/4=%d", n_in, p->ndocs / 4);
     RUN(flmr_launch_filter_local_keys(global_s2, nqueries, n_in, s->ix->pid_base, s->ix->num_passages, s->s2_pids,
@@ -842,8 +880,8 @@ extern "C" int flmr_searcher_tap(flmr_searcher_t* s, int32_t what, int32_t q, vo
         const int rc = poll_status(s, true);
         if (rc) return rc;
     }
-    flmr_opt_scope scope(&s->opt);
     const flmr_index* ix = s->ix;
+    const flmr_plan& pl = s->last_plan;
     const void* src = nullptr;
     int64_t n = 0;
     size_t esz = 4;
@@ -851,7 +889,7 @@ extern "C" int flmr_searcher_tap(flmr_searcher_t* s, int32_t what, int32_t q, vo
     const int nd4 = s->maxp.ndocs / 4;
     switch (what) {
         case FLMR_TAP_CENTROID_SCORES:
-            if (!s->last_full_table) FLMR_FAIL(FLMR_ERR_INVALID, "the last batch ran with the sparse score table: call flmr_searcher_set_full_table(s, 1) first");
+            if (pl.sparse) FLMR_FAIL(FLMR_ERR_INVALID, "the last batch ran with the sparse score table: call flmr_searcher_set_full_table(s, 1) first");
             n = (int64_t)ix->K * s->last_ncol; src = s->cs + (size_t)q * n; break;
         case FLMR_TAP_IDX_BITS:
             n = s->idx_words; src = s->idx_bits + (size_t)q * n; break;
@@ -859,11 +897,11 @@ extern "C" int flmr_searcher_tap(flmr_searcher_t* s, int32_t what, int32_t q, vo
             FLMR_HIP(hipMemcpy(&c, s->ncell + q, 4, hipMemcpyDeviceToHost));
             n = c; src = s->cells + (size_t)q * s->max_cells; break;
         case FLMR_TAP_CANDIDATES:
-            if (s->last_scatter) {  // the hot path skipped the ascending lists: build them now from the bitmaps
+            if (s->last_cand_lazy) {  // the hot path skipped the ascending lists: build them now from the bitmaps
                 int rc = flmr_launch_cand_emit_all(s->last_ca, s->last_stream);
                 if (rc) return rc;
                 FLMR_HIP(hipStreamSynchronize(s->last_stream));
-                s->last_scatter = false;
+                s->last_cand_lazy = false;
             }
             FLMR_HIP(hipMemcpy(&c, s->cand_count + q, 4, hipMemcpyDeviceToHost));
             n = c; src = s->cand + (size_t)q * s->cand_cap; break;
@@ -877,11 +915,11 @@ extern "C" int flmr_searcher_tap(flmr_searcher_t* s, int32_t what, int32_t q, vo
             FLMR_HIP(hipMemcpy(&c, s->s2_count + q, 4, hipMemcpyDeviceToHost));
             n = c; src = s->doc_scores + (size_t)q * nd4; break;
         case FLMR_TAP_Q_ERR:
-            n = s->last_hi_first ? 32 : 0; src = s->q_err + (size_t)q * s->ncol_max; break;
+            n = pl.hi_first ? 32 : 0; src = s->q_err + (size_t)q * s->ncol_max; break;
         case FLMR_TAP_Q_ERR_SUM:
-            n = s->last_hi_first ? 1 : 0; src = s->q_err_sum + q; break;
+            n = pl.hi_first ? 1 : 0; src = s->q_err_sum + q; break;
         case FLMR_TAP_STAGE1_FORM:
-            {   // 7: a query over the score-row capacity (stage 1 recomputed from the centroids)
+            if (pl.qualifying) {   // 7: a query over the score-row capacity (stage 1 recomputed from the centroids)
                 int32_t ro = 0;
                 FLMR_HIP(hipMemcpy(&ro, s->row_ovf + q, 4, hipMemcpyDeviceToHost));
                 if (ro) {
@@ -891,7 +929,7 @@ extern "C" int flmr_searcher_tap(flmr_searcher_t* s, int32_t what, int32_t q, vo
                     return FLMR_OK;
                 }
             }
-            if (s->last_dense) {   // a query the dense forms took: 5 (images + band) / 6 (exact rows)
+            if (pl.dense) {   // a query the dense forms took: 5 (images + band) / 6 (exact rows)
                 int32_t m = 0;
                 FLMR_HIP(hipMemcpy(&m, s->s1d_mode + q, 4, hipMemcpyDeviceToHost));
                 if (m != FLMR_S1D_SKIP) {
@@ -901,7 +939,7 @@ extern "C" int flmr_searcher_tap(flmr_searcher_t* s, int32_t what, int32_t q, vo
                     return FLMR_OK;
                 }
             }
-            n = (s->last_ca.scatter && s->last_ca.fast_state) ? 1 : 0; src = s->cand_fast + FLMR_FAST_HDR + q; break;
+            n = (pl.scatter && s->last_ca.fast_state) ? 1 : 0; src = s->cand_fast + FLMR_FAST_HDR + q; break;
         default: FLMR_FAIL(FLMR_ERR_INVALID, "unknown tap %d", what);
     }
     *count = n;

@@ -1185,89 +1185,113 @@ __global__ __launch_bounds__(256) void s0_postprocess_table(flmr_s0_args a) {
     }
 }
 
-enum { S0_F16 = 0, S0_F32 = 1, S0_VALU = 2 };
+// Stage-0 form: the fp16-split kernels where every centroid is fp16-exact and K % 64 == 0 (query-stationary on the sparse path:
+// qs2 for the "hi first" / fp16-numerics batches, qs otherwise; row-stationary elsewhere), else fp32 MFMA; FLMR_S0_IMPL overrides
+// (f32 / mfma, valu, f16rs: the row-stationary fp16 kernel, qs1: the query-stationary kernel with the dense epilogue in the loop).
+// Also the partial-list geometry that s0_select_cells reads.
+flmr_s0_choice flmr_s0_choose(const flmr_s0_args& a, const flmr_options& o) {
+    flmr_s0_choice ch{};
+    const bool f16_ok = a.centroids_f16_exact && (a.K % (32 * S0_RT) == 0);
+    bool f16 = f16_ok;
+    if (o.s0 == s0_sw::valu || o.s0 == s0_sw::f32) f16 = false;
+    if (!f16) {
+        ch.form = o.s0 == s0_sw::valu ? s0_form::valu : s0_form::f32;
+        ch.nblk = (int)flmr_ceil_div(a.K, 128);
+        return ch;
+    }
+    ch.nblk = (int)flmr_ceil_div(a.K, 32 * S0_RT);
+    ch.part_rows = 32 * S0_RT;
+    const bool sparse = !a.full_table && a.ncol == 32 && !o.s0_staged;
+    const bool qs = sparse && a.centroids_f16 && (int64_t)a.K * 256 < (1ll << 32) && o.s0 != s0_sw::f16rs;
+    if (!qs) {
+        ch.form = sparse ? s0_form::f16_sparse : s0_form::f16_table;
+        return ch;
+    }
+    if ((a.q_hi_only || a.q_err) && o.s0 != s0_sw::qs1 && a.K % (32 * S0Q2_SBT) == 0) {
+        ch.form = s0_form::qs2;
+        // slices on group boundaries when the table allows it: the kernel then also leaves the coarse column maxima
+        const bool grp = a.K % (64 * S0Q2_GRP) == 0 && a.part_idx != nullptr && ch.nblk == a.K / 64 && S0Q2_GROUPS;
+        ch.grp_blocks = grp ? S0Q2_GRP : 0;
+    } else {
+        ch.form = s0_form::qs;
+    }
+    return ch;
+}
 
+// `a` carries the geometry flmr_s0_choose gave for `form` (nblk, part_rows, grp_blocks)
 template <int NC>
-static int launch_s0_t(flmr_s0_args& a, hipStream_t st, int impl) {
+static int launch_s0_t(const flmr_s0_args& a, s0_form form, hipStream_t st) {
     const int qsplit = a.nqueries < 8 ? a.nqueries : 8;
-    a.nblk = (int)flmr_ceil_div(a.K, impl == S0_F16 ? 32 * S0_RT : 128);
-    a.grp_blocks = 0;
-    a.part_rows = impl == S0_F16 ? 32 * S0_RT : 0;
-    if (impl == S0_F16) {
-        const bool sparse_ = !a.full_table && a.ncol == 32 && !flmr_opts().has(FLMR_OPT_S0_STAGED);
-        const bool qs_ = sparse_ && a.centroids_f16 && (int64_t)a.K * 256 < (1ll << 32) && !flmr_opts().is(FLMR_OPT_S0_IMPL, "f16rs");
-        if (qs_) {   // images, bounds and cleared idx words in one launch
-            float* const eb = (a.q_err_buf && !a.q_hi_only) ? a.q_err_buf : nullptr;
-            hipLaunchKernelGGL(s0_prepare_kernel, dim3(a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq, a.nq_cand, a.q_hi, a.q_lo,
-                               a.q_hi_only, a.cen_norm_max, eb, a.q_err_sum, a.idx_bits, a.idx_words);
-        } else {
-            hipLaunchKernelGGL(s0_split_q, dim3((a.ncol * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens,
-                               a.nq, a.nq_cand, a.ncol, a.q_hi, a.q_lo, a.q_hi_only);
-        }
-        const size_t lds = (size_t)S0_WAVES * 32 * S0_LDS_STRIDE * sizeof(float) + (S0_DMA_B ? (size_t)2 * S0_DCH * 2 * 8192 : (size_t)S0_CH * 2 * 32 * S0_BROW * sizeof(_Float16));
-        const bool sparse = !a.full_table && a.ncol == 32 && !flmr_opts().has(FLMR_OPT_S0_STAGED);
-        const dim3 grid((a.nblk + S0_WAVES - 1) / S0_WAVES, qsplit), block(64 * S0_WAVES);
-        const bool qs = sparse && a.centroids_f16 && (int64_t)a.K * 256 < (1ll << 32) && !flmr_opts().is(FLMR_OPT_S0_IMPL, "f16rs");
-        if (!qs) { a.q_err = nullptr; a.q_err_buf = nullptr; }   // the block maxima of the other kernels are the full values: s0_select_cells must not assume otherwise
-        if (qs) {
-            // query-stationary: 16 queries per workgroup, the table cut into as many slices (multiples of 64 rows) as fill the chip
-            const int ngroups = (int)flmr_ceil_div(a.nqueries, 8 * S0Q_QT);
-            int slices = (int)flmr_ceil_div(512, ngroups);  // (256 .. 768 workgroups measure the same)
-            const int max_slices = a.K / 64;
-            if (slices > max_slices) slices = max_slices;
-            const int min_slices = (int)flmr_ceil_div(a.K, S0Q2_MAX_SLICE_ROWS);   // (the flagged-tile lists hold a whole slice)
-            if (slices < min_slices) slices = min_slices;
-            if (slices < 1) slices = 1;
-            const int rows_per_slice = (int)flmr_round_up(flmr_ceil_div(a.K, slices), 64);
-            slices = (int)flmr_ceil_div(a.K, rows_per_slice);
-            const size_t ldsq = (size_t)8 * 32 * S0_LDS_STRIDE * sizeof(float) + (size_t)S0Q_NBUF * 2 * 8192;
-            // (the idx words were cleared and the bounds of this batch's queries written by s0_prepare_kernel above)
-            const bool inline_dense = flmr_opts().is(FLMR_OPT_S0_IMPL, "qs1");   // A/B: the form with the dense epilogue in the loop
-            if ((a.q_hi_only || a.q_err) && !inline_dense && a.K % (32 * S0Q2_SBT) == 0) {
-                const size_t ldsq2 = (size_t)S0Q2_NBUF * S0Q2_SBT * 8192 + (size_t)S0Q2_WAVES * S0Q2_FCAP * sizeof(uint16_t);
-                const int ngroups2 = (int)flmr_ceil_div(a.nqueries, S0Q2_WAVES * S0Q_QT);
-                int slices2 = 512 / ngroups2;   // (rounded down: a few workgroups over 2 x 256 would cost a third round)
-                if (slices2 > a.K / (32 * S0Q2_SBT)) slices2 = a.K / (32 * S0Q2_SBT);
-                if (slices2 < min_slices) slices2 = min_slices;
-                if (slices2 < 1) slices2 = 1;
-                // slices on group boundaries when the table allows it: the kernel then also leaves the coarse column maxima
-                const bool grp = a.K % (64 * S0Q2_GRP) == 0 && a.part_idx != nullptr && a.nblk == a.K / 64 && S0Q2_GROUPS;
-                const int slice_unit = grp ? 64 * S0Q2_GRP : 32 * S0Q2_SBT;
-                if (grp && slices2 > a.K / slice_unit) slices2 = a.K / slice_unit;
-                const int rows_per_slice2 = (int)flmr_round_up(flmr_ceil_div(a.K, slices2), slice_unit);
-                slices2 = (int)flmr_ceil_div(a.K, rows_per_slice2);
-                a.grp_blocks = grp ? S0Q2_GRP : 0;
-                const int slices = slices2, rows_per_slice = rows_per_slice2;   // (shadow: this branch's own cut)
-                if (a.q_hi_only) {
-                    FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs2<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq2));
-                    hipLaunchKernelGGL(s0_centroid_scores_qs2<true>, dim3(ngroups2, slices), dim3(64 * S0Q2_WAVES), ldsq2, st, a, rows_per_slice);
-                } else {
-                    FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs2<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq2));
-                    hipLaunchKernelGGL(s0_centroid_scores_qs2<false>, dim3(ngroups2, slices), dim3(64 * S0Q2_WAVES), ldsq2, st, a, rows_per_slice);
-                }
-#ifdef S0Q_PROFILE
-                {
-                    unsigned long long hh[8];
-                    (void)hipDeviceSynchronize();
-                    (void)hipMemcpyFromSymbol(hh, HIP_SYMBOL(s0q_prof), sizeof(hh));
-                    fprintf(stderr, "[s0q] workgroups %llu x %d slices rows %d; s_memtime ticks per workgroup: prologue %.0f | per block: dma wait %.1f barrier %.1f body %.1f | "
-                                    "drain %.0f deferred %.0f (blocks per workgroup %.1f)\n", hh[7], slices, rows_per_slice, (double)hh[0] / hh[7],
-                            (double)hh[1] / hh[6], (double)hh[2] / hh[6], (double)hh[3] / hh[6], (double)hh[4] / hh[7], (double)hh[5] / hh[7], (double)hh[6] / hh[7]);
-                    unsigned long long z[8] = {};
-                    (void)hipMemcpyToSymbol(HIP_SYMBOL(s0q_prof), z, sizeof(z));
-                }
-#endif
-            } else if (a.q_hi_only) {
-                FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq));
-                hipLaunchKernelGGL(s0_centroid_scores_qs<true>, dim3(ngroups, slices), dim3(512), ldsq, st, a, rows_per_slice);
-            } else if (a.q_err) {
-                FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq));
-                hipLaunchKernelGGL((s0_centroid_scores_qs<false, true>), dim3(ngroups, slices), dim3(512), ldsq, st, a, rows_per_slice);
+    if (form == s0_form::qs || form == s0_form::qs2) {
+        // query-stationary: 16 queries per workgroup, the table cut into as many slices (multiples of 64 rows) as fill the chip
+        if (a.full_table || a.ncol != 32 || !a.centroids_f16 || (int64_t)a.K * 256 >= (1ll << 32))
+            FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the query-stationary stage 0 needs the sparse table, one column tile and the fp16 centroids");
+        // images, bounds and cleared idx words in one launch
+        float* const eb = (a.q_err_buf && !a.q_hi_only) ? a.q_err_buf : nullptr;
+        hipLaunchKernelGGL(s0_prepare_kernel, dim3(a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq, a.nq_cand, a.q_hi, a.q_lo,
+                           a.q_hi_only, a.cen_norm_max, eb, a.q_err_sum, a.idx_bits, a.idx_words);
+        const int ngroups = (int)flmr_ceil_div(a.nqueries, 8 * S0Q_QT);
+        int slices = (int)flmr_ceil_div(512, ngroups);  // (256 .. 768 workgroups measure the same)
+        const int max_slices = a.K / 64;
+        if (slices > max_slices) slices = max_slices;
+        const int min_slices = (int)flmr_ceil_div(a.K, S0Q2_MAX_SLICE_ROWS);   // (the flagged-tile lists hold a whole slice)
+        if (slices < min_slices) slices = min_slices;
+        if (slices < 1) slices = 1;
+        const int rows_per_slice = (int)flmr_round_up(flmr_ceil_div(a.K, slices), 64);
+        slices = (int)flmr_ceil_div(a.K, rows_per_slice);
+        const size_t ldsq = (size_t)8 * 32 * S0_LDS_STRIDE * sizeof(float) + (size_t)S0Q_NBUF * 2 * 8192;
+        // (the idx words were cleared and the bounds of this batch's queries written by s0_prepare_kernel above)
+        if (form == s0_form::qs2) {
+            if (!(a.q_hi_only || a.q_err) || a.K % (32 * S0Q2_SBT) != 0) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the qs2 stage 0 needs hi-first bounds and K %% %d == 0", 32 * S0Q2_SBT);
+            const size_t ldsq2 = (size_t)S0Q2_NBUF * S0Q2_SBT * 8192 + (size_t)S0Q2_WAVES * S0Q2_FCAP * sizeof(uint16_t);
+            const int ngroups2 = (int)flmr_ceil_div(a.nqueries, S0Q2_WAVES * S0Q_QT);
+            int slices2 = 512 / ngroups2;   // (rounded down: a few workgroups over 2 x 256 would cost a third round)
+            if (slices2 > a.K / (32 * S0Q2_SBT)) slices2 = a.K / (32 * S0Q2_SBT);
+            if (slices2 < min_slices) slices2 = min_slices;
+            if (slices2 < 1) slices2 = 1;
+            const bool grp = a.grp_blocks > 0;
+            const int slice_unit = grp ? 64 * S0Q2_GRP : 32 * S0Q2_SBT;
+            if (grp && slices2 > a.K / slice_unit) slices2 = a.K / slice_unit;
+            const int rows_per_slice2 = (int)flmr_round_up(flmr_ceil_div(a.K, slices2), slice_unit);
+            slices2 = (int)flmr_ceil_div(a.K, rows_per_slice2);
+            const int slices = slices2, rows_per_slice = rows_per_slice2;   // (shadow: this branch's own cut)
+            if (a.q_hi_only) {
+                FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs2<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq2));
+                hipLaunchKernelGGL(s0_centroid_scores_qs2<true>, dim3(ngroups2, slices), dim3(64 * S0Q2_WAVES), ldsq2, st, a, rows_per_slice);
             } else {
-                FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq));
-                hipLaunchKernelGGL(s0_centroid_scores_qs<false>, dim3(ngroups, slices), dim3(512), ldsq, st, a, rows_per_slice);
+                FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs2<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq2));
+                hipLaunchKernelGGL(s0_centroid_scores_qs2<false>, dim3(ngroups2, slices), dim3(64 * S0Q2_WAVES), ldsq2, st, a, rows_per_slice);
             }
-        } else if (sparse) {
+#ifdef S0Q_PROFILE
+            {
+                unsigned long long hh[8];
+                (void)hipDeviceSynchronize();
+                (void)hipMemcpyFromSymbol(hh, HIP_SYMBOL(s0q_prof), sizeof(hh));
+                fprintf(stderr, "[s0q] workgroups %llu x %d slices rows %d; s_memtime ticks per workgroup: prologue %.0f | per block: dma wait %.1f barrier %.1f body %.1f | "
+                                "drain %.0f deferred %.0f (blocks per workgroup %.1f)\n", hh[7], slices, rows_per_slice, (double)hh[0] / hh[7],
+                        (double)hh[1] / hh[6], (double)hh[2] / hh[6], (double)hh[3] / hh[6], (double)hh[4] / hh[7], (double)hh[5] / hh[7], (double)hh[6] / hh[7]);
+                unsigned long long z[8] = {};
+                (void)hipMemcpyToSymbol(HIP_SYMBOL(s0q_prof), z, sizeof(z));
+            }
+#endif
+        } else if (a.q_hi_only) {
+            FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq));
+            hipLaunchKernelGGL(s0_centroid_scores_qs<true>, dim3(ngroups, slices), dim3(512), ldsq, st, a, rows_per_slice);
+        } else if (a.q_err) {
+            FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq));
+            hipLaunchKernelGGL((s0_centroid_scores_qs<false, true>), dim3(ngroups, slices), dim3(512), ldsq, st, a, rows_per_slice);
+        } else {
+            FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_qs<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq));
+            hipLaunchKernelGGL(s0_centroid_scores_qs<false>, dim3(ngroups, slices), dim3(512), ldsq, st, a, rows_per_slice);
+        }
+    } else if (form == s0_form::f16_sparse || form == s0_form::f16_table) {
+        // (the block maxima of these kernels are the full values: the caller passes no q_err, s0_select_cells must not assume otherwise)
+        if (a.q_err) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the row-stationary stage 0 leaves no hi-first bounds");
+        hipLaunchKernelGGL(s0_split_q, dim3((a.ncol * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens,
+                           a.nq, a.nq_cand, a.ncol, a.q_hi, a.q_lo, a.q_hi_only);
+        const size_t lds = (size_t)S0_WAVES * 32 * S0_LDS_STRIDE * sizeof(float) + (S0_DMA_B ? (size_t)2 * S0_DCH * 2 * 8192 : (size_t)S0_CH * 2 * 32 * S0_BROW * sizeof(_Float16));
+        const dim3 grid((a.nblk + S0_WAVES - 1) / S0_WAVES, qsplit), block(64 * S0_WAVES);
+        if (form == s0_form::f16_sparse) {
             FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_f16<false, true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL((s0_centroid_scores_f16<false, true>), grid, block, lds, st, a);
@@ -1276,7 +1300,7 @@ static int launch_s0_t(flmr_s0_args& a, hipStream_t st, int impl) {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL((s0_centroid_scores_f16<false, false>), grid, block, lds, st, a);
         }
-    } else if (impl == S0_F32) {
+    } else if (form == s0_form::f32) {
         hipLaunchKernelGGL(s0_centroid_scores_mfma<NC>, dim3(a.nblk, qsplit), dim3(256), 0, st, a);
     } else {
         hipLaunchKernelGGL(s0_centroid_scores_valu, dim3(1024, a.nqueries), dim3(256), 0, st, a);
@@ -1317,7 +1341,7 @@ __global__ __launch_bounds__(256) void s0_argmax_reduce(flmr_s0_args a, int32_t*
 
 // a: centroids (fp16-exact, K % 64 == 0), Q = the embeddings viewed as [nqueries, 32, 128], q_lens (last query may be short),
 // q_hi/q_lo, part_val/part_idx [nqueries, K/64, 32], idx_bits [nqueries, K/32] (scratch).  out_codes [nqueries * 32].
-int flmr_launch_centroid_argmax(flmr_s0_args& a, int32_t* out_codes, hipStream_t st) {
+int flmr_launch_centroid_argmax(flmr_s0_args a, int32_t* out_codes, hipStream_t st) {
     if (a.K % (32 * S0_RT) != 0 || a.ncol != 32 || a.nq != 32) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "centroid argmax needs K %% 64 == 0 and 32-column tiles");
     a.nblk = a.K / (32 * S0_RT);
     a.part_rows = 32 * S0_RT;
@@ -1344,20 +1368,17 @@ int flmr_launch_split_q(const flmr_s0_args& a, hipStream_t st) {
 
 static int nc_bucket(int ncells) { return ncells <= 1 ? 1 : ncells <= 2 ? 2 : ncells <= 4 ? 4 : 8; }
 
-// FLMR_S0_IMPL = f16 (default when every centroid is fp16-exact) | f32 (fp32 MFMA) | valu (plain FMA cross-check)
-int flmr_launch_centroid_scores(flmr_s0_args& a, hipStream_t st) {
-    const flmr_options& o = flmr_opts();
-    const char* env = o.has(FLMR_OPT_S0_IMPL) ? o.v[FLMR_OPT_S0_IMPL] : nullptr;
-    const bool f16_ok = a.centroids_f16_exact && (a.K % (32 * S0_RT) == 0);
-    int impl = f16_ok ? S0_F16 : S0_F32;
-    if (env && strcmp(env, "valu") == 0) impl = S0_VALU;
-    if (env && (strcmp(env, "f32") == 0 || strcmp(env, "mfma") == 0)) impl = S0_F32;
-    if (env && (strcmp(env, "f16") == 0 || strcmp(env, "f16rs") == 0) && f16_ok) impl = S0_F16;
+int flmr_launch_centroid_scores(const flmr_s0_args& a, s0_form form, hipStream_t st) {
+    const bool f16 = form != s0_form::f32 && form != s0_form::valu;
+    if (f16 && !(a.centroids_f16_exact && a.K % (32 * S0_RT) == 0))
+        FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the fp16 stage 0 needs fp16-exact centroids and K %% %d == 0", 32 * S0_RT);
+    if (a.nblk != (int)flmr_ceil_div(a.K, f16 ? 32 * S0_RT : 128) || a.part_rows != (f16 ? 32 * S0_RT : 0))
+        FLMR_FAIL(FLMR_ERR_INVALID, "stage-0 arguments without the geometry of the chosen form (flmr_s0_choose)");
     switch (nc_bucket(a.ncells)) {
-        case 1: return launch_s0_t<1>(a, st, impl);
-        case 2: return launch_s0_t<2>(a, st, impl);
-        case 4: return launch_s0_t<4>(a, st, impl);
-        default: return launch_s0_t<8>(a, st, impl);
+        case 1: return launch_s0_t<1>(a, form, st);
+        case 2: return launch_s0_t<2>(a, form, st);
+        case 4: return launch_s0_t<4>(a, form, st);
+        default: return launch_s0_t<8>(a, form, st);
     }
 }
 

@@ -858,18 +858,14 @@ int flmr_launch_s1_image(const flmr_s1d_args& a_in, double mean_codes, hipStream
     return FLMR_OK;
 }
 
-// one block: mode / scan_skip per query, and any[0] = some query takes the image form, any[1] = some query takes the exact pass (a band
+// one block: mode / scan_skip per query (nqual / row_ovf NULL: qualifying_kernel did not run in this batch), and any[0] = some query takes the image form, any[1] = some query takes the exact pass (a band
 // or a whole list): the dense kernels read their word first and leave at once when it is 0 (the usual case on the tuned path)
 __global__ __launch_bounds__(1024) void s1_dense_modes_kernel(const int32_t* skip, const int32_t* nqual, const int32_t* row_ovf, int32_t nqueries,
                                                               int32_t img_rows, int32_t exact_too, int32_t* mode, int32_t* scan_skip, int32_t* any) {
     int any_img = 0, any_exact = 0;
     for (int q = threadIdx.x; q < nqueries; q += 1024) {
-        int m = FLMR_S1D_SKIP, sk = 1;
-        if (!(skip && skip[q]) && !(row_ovf && row_ovf[q])) {
-            if (nqual[q] <= img_rows) m = FLMR_S1D_IMAGE;
-            else if (exact_too) m = FLMR_S1D_EXACT;
-            else sk = 0;   // the scan takes the query
-        }
+        int sk;
+        const int m = flmr_s1_query_form((skip && skip[q]) || (row_ovf && row_ovf[q]), nqual ? nqual[q] : 0x7fffffff, img_rows, exact_too, &sk);
         mode[q] = m;
         scan_skip[q] = sk;
         any_img |= m == FLMR_S1D_IMAGE;

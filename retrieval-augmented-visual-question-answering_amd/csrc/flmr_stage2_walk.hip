@@ -147,12 +147,12 @@ __global__ __launch_bounds__(256) void tile_centroids_kernel(const _Float16* __r
 // K by ~0.6 * 1024 * mean passage length whatever ndocs is -- BASELINE's 1 M / 6 M-passage indexes (K = 2^17, 2^18) never take
 // the walk and do not pay for the copy -- or where FLMR_S2_IMPL=walk forces it.  A failed allocation only makes the walk
 // unavailable.
-int flmr_build_tiled_centroids(flmr_index* ix) {
+int flmr_build_tiled_centroids(flmr_index* ix, bool forced) {
     ix->centroids_f16_tiled = nullptr;
     if (!ix->centroids_f16 || ix->K % 32 != 0 || !ix->codes_sorted) return FLMR_OK;
     const double mean_len = (double)ix->N / (double)(ix->num_passages > 0 ? ix->num_passages : 1);
     const bool can_pay = (double)ix->K <= 0.6 * W2_DOCS * mean_len;
-    if (!can_pay && !flmr_process_options().is(FLMR_OPT_S2_IMPL, "walk")) return FLMR_OK;
+    if (!can_pay && !forced) return FLMR_OK;
     if (hipMalloc(reinterpret_cast<void**>(&ix->centroids_f16_tiled), (size_t)ix->K * FLMR_DIM * sizeof(_Float16)) != hipSuccess) {
         (void)hipGetLastError();
         ix->centroids_f16_tiled = nullptr;

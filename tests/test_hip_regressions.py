@@ -551,3 +551,34 @@ def test_scoring_surface_flipr_l2_and_the_cross_form(hip):
         for q in range(7):
             one = ops.colbert_score_padded(Qs[q:q + 1], Ds, mask).cpu()
             assert torch.equal(cross[q].view(torch.int32), one.view(torch.int32)), (dim, q)
+
+
+@pytest.mark.parametrize("nq_cand,env", [(64, {}), (32, {"FLMR_S1_IMPL": "scan"}), (32, {"FLMR_CAND_IMPL": "atomic"})],
+                         ids=["nq_cand64", "scan", "atomic"])
+def test_stage1_without_surviving_centroids_matches_the_oracle(hip, nq_cand, env):
+    """A threshold above every centroid score leaves nqual == 0 for every query.  Where the dense stage-1 forms do not run (two
+    column tiles, FLMR_S1_IMPL=scan, FLMR_CAND_IMPL=atomic) such a query must still be scanned: its stage-1 keys are this batch's,
+    not what FLMR_POISON left in the workspace, and the result is the oracle's."""
+    nat = hip["native"]
+    from ravqa_amd import synth
+    from ravqa_amd.scorer import IndexScorer
+    corpus = synth.make_corpus(6000, (3, 70), 2048, 2, seed=41, device="cuda")
+    oi = _oracle(corpus)
+    Q, _ = synth.make_queries(corpus, 8, 64, seed=7)
+    ncells, thr, ndocs = 2, 1.0e4, 256
+    with nat.options(FLMR_POISON="1", **env):
+        scorer = IndexScorer(device_index=synth.corpus_device_index(corpus), max_batch=8)
+        p, s, c = scorer.search_batch(Q, ndocs // 4, ncells, thr, ndocs, nq_cand)
+        scorer.check()
+    p, s, c = p.cpu().numpy(), s.cpu().numpy(), c.cpu().numpy()
+    Qh = Q.cpu().numpy()
+    checked = 0
+    for i in range(Qh.shape[0]):
+        rp, rs, ncand = oi.rank(Qh[i], ncells, thr, ndocs, nq_cand)
+        if ncand < ndocs:
+            continue
+        m = int(c[i])
+        assert m == len(rp), (i, m, len(rp))
+        tie_aware_equal(rp, rs, p[i, :m], s[i, :m])
+        checked += 1
+    assert checked >= 4, checked

@@ -473,3 +473,35 @@ def test_score_reduce_interactions_and_l2_on_the_host():
     D = torch.randn(B, Ld, 16, generator=g)
     want = (-1.0 * ((Q.unsqueeze(2) - D.unsqueeze(1)) ** 2).sum(-1)).max(-1).values.sum(-1)
     assert torch.equal(model.score(Q, D, mask), want)
+
+
+def test_switch_values_are_parsed_and_checked():
+    """flmr_set_option accepts exactly the values the library names (those the tests use included) and rejects any other with
+    FLMR_ERR_INVALID and the accepted values in flmr_last_error(); needs the built library, no device."""
+    lib = _native.load(require_device=False)
+    accepted = {
+        "FLMR_S0_IMPL": ["qs1", "f16", "f16rs", "f32", "mfma", "valu"],
+        "FLMR_S1_IMPL": ["scan", "slots", "image"],
+        "FLMR_S2_IMPL": ["xcda", "xcd", "walk", "lds"],
+        "FLMR_S3_IMPL": ["qs", "lean", "cw", "cwregs", "dma", "regs", "f32"],
+        "FLMR_CAND_IMPL": ["atomic"],
+        "FLMR_SCORE_IMPL": ["valu"],
+        "FLMR_FULL_TABLE": ["1"], "FLMR_S1_NO_HITMAP": ["1"], "FLMR_S0_STAGED": ["1"], "FLMR_S3_NO_MULTIQ": ["1"],
+        "FLMR_POISON": ["1"], "FLMR_ROW_CAP": ["256", "64", "65535"],
+    }
+    try:
+        for name, values in accepted.items():
+            for v in values:
+                assert lib.flmr_set_option(name.encode(), v.encode()) == 0, (name, v, lib.flmr_last_error())
+            assert lib.flmr_set_option(name.encode(), None) == 0
+        assert lib.flmr_set_option(b"FLMR_S2_IMPL", b"xdc") == 1
+        err = lib.flmr_last_error().decode()
+        assert "FLMR_S2_IMPL=xdc" in err and all(v in err.split() for v in accepted["FLMR_S2_IMPL"]), err
+        for name, bad in (("FLMR_S0_IMPL", "f64"), ("FLMR_S1_IMPL", "narrow"), ("FLMR_S3_IMPL", "QS"), ("FLMR_CAND_IMPL", "chunked"),
+                          ("FLMR_SCORE_IMPL", "mfma"), ("FLMR_ROW_CAP", "lots"), ("FLMR_S1_IMPL", "x" * 40)):
+            assert lib.flmr_set_option(name.encode(), bad.encode()) == 1, (name, bad)
+            assert name in lib.flmr_last_error().decode()
+        assert lib.flmr_set_option(b"FLMR_NOT_A_SWITCH", b"1") == 1 and b"unknown option" in lib.flmr_last_error()
+    finally:
+        for name in accepted:
+            lib.flmr_set_option(name.encode(), None)
