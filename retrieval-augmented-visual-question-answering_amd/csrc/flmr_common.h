@@ -58,8 +58,10 @@ struct flmr_options {
     bool s0_staged;           // FLMR_S0_STAGED: staged epilogue for every tile
     bool s3_no_multiq;        // FLMR_S3_NO_MULTIQ: single-tile MaxSim kernel for long queries too
     bool score_valu;          // FLMR_SCORE_IMPL=valu: plain-FMA padded scorer
-    bool poison;              // FLMR_POISON (test runs): every batch starts with its per-query score rows, ranks and survivor lists filled
-                              // with 0xFF -- a stage that lives off an earlier batch's workspace then produces NaNs / wild indices
+    bool poison;              // FLMR_POISON (test runs): every batch and every phase 1 starts with EVERY scratch buffer of the searcher's
+                              // workspace refilled over its whole allocation (the record kept by ws_alloc, flmr_search.hip): floats, halves
+                              // and 64-bit keys with 0xFF bytes, counts / offsets / ids / masks with 0 -- a stage that lives off an earlier
+                              // batch's workspace then produces NaNs or loses its survivors; only the deferred status words are carried
     int32_t row_cap;          // FLMR_ROW_CAP: score rows a searcher keeps per query (64 .. 65535; 0 = the default 16384, at most K): a query
                               // with more centroids above the threshold has its stage 1 recomputed
 };

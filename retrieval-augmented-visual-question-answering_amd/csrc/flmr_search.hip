@@ -34,8 +34,24 @@ struct flmr_plan {
     s3_form s3;
 };
 
+// ---- the workspace record: every device buffer of a searcher, with what FLMR_POISON does to it ---------------------------------
+// scratch: no batch may read what an earlier batch left in it.  FLMR_POISON fills the WHOLE allocation at the start of every batch
+//          and of every phase 1 -- WS_FF: floats, halves and 64-bit keys get 0xFF bytes (NaNs; keys above every real key that carry
+//          pid -1); WS_ZERO: counts, offsets, ranks, ids, flags and bit masks get 0, in range for every consumer (a query that lives
+//          off them loses its survivors, which the result shows).
+// carried: state that legitimately outlives a batch; never poisoned (the reason stands at the allocation).
+enum ws_kind : uint8_t { WS_FF, WS_ZERO, WS_CARRIED };
+struct ws_rec {
+    void* ptr;
+    size_t bytes;
+    ws_kind kind;
+    size_t phase_row;   // > 0: no phase reads what an earlier phase left in it either -- phases 2 / 3 fill the batch's rows of this many bytes
+};
+#define FLMR_WS_MAX 64
+
 struct flmr_searcher {
     const flmr_index* ix;
+    ws_rec ws[FLMR_WS_MAX]; int32_t nws;   // every device buffer below: what destroy frees and what the poison walks
     int32_t max_queries, max_nq;
     flmr_search_params_t maxp;
     int32_t ncol_max, idx_words, nblk, max_cells, nc_bucket;
@@ -87,11 +103,39 @@ struct flmr_searcher {
 
 static int nc_bucket_of(int ncells) { return ncells <= 1 ? 1 : ncells <= 2 ? 2 : ncells <= 4 ? 4 : 8; }
 
+// One workspace buffer: allocated, counted and recorded with its kind.  `phase_rows`: see ws_rec::phase_row (count / phase_rows
+// elements per query).  A failed hipMalloc leaves *p NULL and no record: the optional buffers' callers go on without them.
 template <typename T>
-static int ws_alloc(flmr_searcher* s, T** p, size_t count) {
+static int ws_alloc(flmr_searcher* s, T** p, size_t count, ws_kind kind, size_t phase_rows = 0) {
     const size_t bytes = (count ? count : 1) * sizeof(T);
+    *p = nullptr;
+    if (s->nws >= FLMR_WS_MAX) FLMR_FAIL(FLMR_ERR_INVALID, "workspace record full (FLMR_WS_MAX=%d)", FLMR_WS_MAX);
     FLMR_HIP(hipMalloc(reinterpret_cast<void**>(p), bytes));
     s->bytes += (int64_t)bytes;
+    s->ws[s->nws++] = ws_rec{*p, bytes, kind, phase_rows ? bytes / phase_rows : 0};
+    return FLMR_OK;
+}
+template <typename T>
+static bool ws_alloc_optional(flmr_searcher* s, T** p, size_t count, ws_kind kind) {
+    if (ws_alloc(s, p, count, kind) == FLMR_OK) return true;
+    (void)hipGetLastError();
+    *p = nullptr;
+    return false;
+}
+static void ws_release_last(flmr_searcher* s) {   // (an optional buffer whose companion could not be had)
+    const ws_rec& r = s->ws[--s->nws];
+    (void)hipFree(r.ptr);
+    s->bytes -= (int64_t)r.bytes;
+}
+
+// FLMR_POISON: the walk over the record.  `first_phase`: the call starts a batch (flmr_search_batch, phase 1, the probe) -- every
+// scratch buffer, whole; else (phase 2 / 3) only the buffers no phase hands on, the batch's rows
+static int ws_poison(flmr_searcher* s, int32_t nqueries, bool first_phase, hipStream_t st) {
+    for (int i = 0; i < s->nws; i++) {
+        const ws_rec& r = s->ws[i];
+        if (r.kind == WS_CARRIED || !(first_phase || r.phase_row)) continue;
+        FLMR_HIP(hipMemsetAsync(r.ptr, r.kind == WS_FF ? 0xFF : 0, first_phase ? r.bytes : (size_t)nqueries * r.phase_row, st));
+    }
     return FLMR_OK;
 }
 
@@ -131,10 +175,13 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
     if (s->cand_cap < 1) s->cand_cap = 1;
     const size_t B = (size_t)max_queries;
     const int nd = maxp->ndocs, nd4 = maxp->ndocs / 4;
-#define WS(ptr, count)                          \
-    do {                                        \
-        rc = ws_alloc(s, &s->ptr, (count));     \
-        if (rc) { flmr_searcher_destroy(s); return rc; } \
+    // WS(buffer, elements, kind[, B]): the kind is the buffer's FLMR_POISON class (ws_kind above); a trailing B marks the six buffers
+    // FLMR_POISON has filled since round 4, which phases 2 / 3 fill too (their pattern stays 0xFF, ranks and ids included: no
+    // consumer reads them before their writer in any phase)
+#define WS(ptr, count, ...)                                  \
+    do {                                                     \
+        rc = ws_alloc(s, &s->ptr, (count), __VA_ARGS__);     \
+        if (rc) { flmr_searcher_destroy(s); return rc; }     \
     } while (0)
     // The full K x ncol score table per query (16.8 MB at K = 131072) is allocated on first use by a batch that needs it
     // (full-table mode: taps / retrieve(), centroids that are not fp16-exact, nq_cand > 32); the default path keeps only the
@@ -144,89 +191,85 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
         const int32_t cap = s->opt.row_cap ? s->opt.row_cap : 16384;   // (at most 65535: the code-scanning stage 1 keeps 16-bit ranks in LDS)
         s->row_cap = cap < ix->K ? cap : ix->K;
     }
-    WS(rows, B * (size_t)s->row_cap * 32);
-    WS(idx_prefix, B * (size_t)s->idx_words);
-    WS(idx_bits, B * (size_t)s->idx_words);
-    WS(part_val, B * (size_t)s->nblk * s->ncol_max * s->nc_bucket);
-    WS(part_idx, B * (size_t)s->nblk * s->ncol_max * s->nc_bucket);
-    WS(cells, B * (size_t)s->max_cells);
-    WS(ncell, B);
-    WS(bitmap, B * (size_t)s->bitmap_words);
-    WS(cand, B * (size_t)s->cand_cap);
-    WS(cand_count, B);
-    WS(keys1, B * (size_t)s->cand_cap);
-    WS(s1_pids, B * (size_t)nd);
-    WS(s1_count, B);
-    WS(keys2, B * (size_t)nd);
-    WS(s2_pids, B * (size_t)nd4);
-    WS(s2_count, B);
-    WS(keys3, B * (size_t)nd4);
-    WS(doc_scores, B * (size_t)nd4);
-    WS(overflow, 4);
-    WS(q_lens_ws, B);
-    WS(q_hi, B * (size_t)s->ncol_max * FLMR_DIM);
-    WS(q_lo, B * (size_t)s->ncol_max * FLMR_DIM);
-    WS(q_err, B * (size_t)s->ncol_max);
-    WS(q_err_sum, B);
-    WS(s2_band, B * (size_t)nd);
-    WS(s2_band_count, B);
-    WS(s2_need, B);
-    WS(s2_def, B);
-    WS(keys2b, B * (size_t)nd);
-    WS(hit_bits, B * (size_t)s->bitmap_words);
-    WS(hit_valid, B);
-    WS(key_count, B);
-    WS(s1_slot, B * (size_t)nd);
-    WS(s2_slot, B * (size_t)nd4);
+    // stage 0 -> candidates -> stage 1.  Everything a phase hands on (q_hi / q_lo to phase 2, the status words) or a tap reads
+    // after the batch (idx_bits, cells, cand, the survivor lists, doc_scores, the form words) stays valid until the next batch or
+    // phase 1 starts: that is where the scratch kinds are filled, so none of them needs the carried kind.
+    WS(rows, B * (size_t)s->row_cap * 32, WS_FF, B);            // float score rows
+    WS(idx_prefix, B * (size_t)s->idx_words, WS_FF, B);         // ranks (the round-4 pattern)
+    WS(idx_bits, B * (size_t)s->idx_words, WS_ZERO);            // centroid mask: no survivor
+    WS(part_val, B * (size_t)s->nblk * s->ncol_max * s->nc_bucket, WS_FF);     // float block maxima / list values
+    WS(part_idx, B * (size_t)s->nblk * s->ncol_max * s->nc_bucket, WS_ZERO);   // centroid ids (or the coarse maxima: 0.0f)
+    WS(cells, B * (size_t)s->max_cells, WS_ZERO);               // centroid ids
+    WS(ncell, B, WS_ZERO);
+    WS(bitmap, B * (size_t)s->bitmap_words, WS_ZERO);           // passage mask
+    WS(cand, B * (size_t)s->cand_cap, WS_ZERO);                 // pids
+    WS(cand_count, B, WS_ZERO);
+    WS(keys1, B * (size_t)s->cand_cap, WS_FF, B);
+    WS(s1_pids, B * (size_t)nd, WS_ZERO);
+    WS(s1_count, B, WS_ZERO);
+    WS(keys2, B * (size_t)nd, WS_FF, B);
+    WS(s2_pids, B * (size_t)nd4, WS_ZERO);
+    WS(s2_count, B, WS_ZERO);
+    WS(keys3, B * (size_t)nd4, WS_FF, B);
+    WS(doc_scores, B * (size_t)nd4, WS_FF);                     // float
+    WS(overflow, 4, WS_CARRIED);                                // the deferred status: raised by a batch, read and cleared by a later call
+    WS(q_lens_ws, B, WS_ZERO);                                  // lengths in [0, nq] (filled BEFORE the batch's lengths are written)
+    WS(q_hi, B * (size_t)s->ncol_max * FLMR_DIM, WS_FF);        // halves; phase 1's images are phase 2's
+    WS(q_lo, B * (size_t)s->ncol_max * FLMR_DIM, WS_FF);
+    WS(q_err, B * (size_t)s->ncol_max, WS_FF);                  // float bounds
+    WS(q_err_sum, B, WS_FF);
+    WS(s2_band, B * (size_t)nd, WS_ZERO);                       // pids
+    WS(s2_band_count, B, WS_ZERO);
+    WS(s2_need, B, WS_ZERO);
+    WS(s2_def, B, WS_ZERO);
+    WS(keys2b, B * (size_t)nd, WS_FF);
+    WS(hit_bits, B * (size_t)s->bitmap_words, WS_ZERO);         // passage mask
+    WS(hit_valid, B, WS_ZERO);                                  // flag: 0 = not a list-scatter query
+    WS(key_count, B, WS_ZERO);
+    WS(s1_slot, B * (size_t)nd, WS_ZERO);                       // positions in the global lists (written and read inside one phase)
+    WS(s2_slot, B * (size_t)nd4, WS_ZERO);
     if (ix->doc_splits && s->ncol_max == 32 && (flmr_stage2_xcd_pays(ix) || s->opt.s2 == s2_sw::xcd)) {
         // optional: without it (1 KB per query and survivor; e.g. out of memory) stage 2 runs in its gather form
-        const size_t bytes = flmr_stage2_xcd_part_floats(ix, (int64_t)B, nd) * sizeof(float);
-        if (hipMalloc(reinterpret_cast<void**>(&s->s2_part), bytes) == hipSuccess) s->bytes += (int64_t)bytes;
-        else { s->s2_part = nullptr; (void)hipGetLastError(); }
+        (void)ws_alloc_optional(s, &s->s2_part, flmr_stage2_xcd_part_floats(ix, (int64_t)B, nd), WS_FF);   // float column maxima
     }
     s->qmax = s->row_cap;
-    WS(qual, B * (size_t)s->qmax);
-    WS(nqual, B);
-    WS(chunk_cnt, B * (size_t)ix->nchunks);
-    WS(chunk_hits, B * (size_t)ix->nchunks);
-    WS(cand_hit, B * (size_t)s->cand_cap);
+    WS(qual, B * (size_t)s->qmax, WS_FF, B);                    // centroid ids (the round-4 pattern)
+    WS(nqual, B, WS_ZERO);
+    WS(chunk_cnt, B * (size_t)ix->nchunks, WS_ZERO);
+    WS(chunk_hits, B * (size_t)ix->nchunks, WS_ZERO);
+    WS(cand_hit, B * (size_t)s->cand_cap, WS_ZERO);             // byte flags
     // dense stage 1: needs the sorted code copy (whole 16-byte pieces are read: its padding) and 32-bit token offsets
     s->s1d_img_rows = (ix->codes_sorted && s->ncol_max == 32 && s->opt.s1 != s1_sw::scan) ? flmr_s1_dense_image_rows(max_queries, s->idx_words, ix->mean_ulen) : 0;
-    WS(s1d_any, 16); WS(s1d_mode, B); WS(s1d_band_count, B); WS(s1d_err, B); WS(s1d_in_count, B); WS(s1d_scan_skip, B); WS(row_ovf, B);
-    if (s->s1d_img_rows > 0) WS(s1d_band, B * (size_t)s->cand_cap);
-    WS(q3_hi, B * (size_t)flmr_round_up(max_nq, 32) * FLMR_DIM);
-    WS(q3_lo, B * (size_t)flmr_round_up(max_nq, 32) * FLMR_DIM);
-#undef WS
+    WS(s1d_any, 16, WS_ZERO);                                   // flags + item counters: no query takes a dense pass
+    WS(s1d_mode, B, WS_ZERO);                                   // FLMR_S1D_SKIP
+    WS(s1d_band_count, B, WS_ZERO);
+    WS(s1d_err, B, WS_FF);                                      // float
+    WS(s1d_in_count, B, WS_ZERO);
+    WS(s1d_scan_skip, B, WS_ZERO);
+    WS(row_ovf, B, WS_ZERO);                                    // flag
+    if (s->s1d_img_rows > 0) WS(s1d_band, B * (size_t)s->cand_cap, WS_ZERO);   // pids
+    WS(q3_hi, B * (size_t)flmr_round_up(max_nq, 32) * FLMR_DIM, WS_FF);        // halves
+    WS(q3_lo, B * (size_t)flmr_round_up(max_nq, 32) * FLMR_DIM, WS_FF);
     {   // optional workspace of the planned-tile S3 kernel: one 8-byte descriptor per 32-token tile of a query's finalists
         s->s3_desc_stride = (int64_t)nd4 * ((ix->max_doclen + 31) / 32);
         s->s3_wcap = nd4 + 8;
-        const size_t db = B * (size_t)s->s3_desc_stride * sizeof(uint2), wb = B * (size_t)s->s3_wcap * sizeof(int32_t);
-        if (s->s3_desc_stride > 0 && db <= ((size_t)1 << 30) && hipMalloc(reinterpret_cast<void**>(&s->s3_desc), db) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void**>(&s->s3_wbeg), wb) == hipSuccess) {
-            s->bytes += (int64_t)(db + wb);
-        } else {
-            (void)hipGetLastError();
-            (void)hipFree(s->s3_desc); (void)hipFree(s->s3_wbeg);
-            s->s3_desc = nullptr; s->s3_wbeg = nullptr;
+        const size_t db = B * (size_t)s->s3_desc_stride * sizeof(uint2);
+        if (s->s3_desc_stride > 0 && db <= ((size_t)1 << 30) && ws_alloc_optional(s, &s->s3_desc, B * (size_t)s->s3_desc_stride, WS_ZERO) &&   // (token offset, slot)
+            !ws_alloc_optional(s, &s->s3_wbeg, B * (size_t)s->s3_wcap, WS_ZERO)) {                                                            // tile offsets
+            ws_release_last(s);   // both or neither
+            s->s3_desc = nullptr;
         }
         if (s->s3_desc && max_nq > 32) {
             s->s3_colmax_cap = (int64_t)B * nd4 * flmr_round_up(max_nq, 32) + (int64_t)B;   // (+ the per-query output scales of the query-stationary kernel)
-            if (s->s3_colmax_cap * (int64_t)sizeof(float) <= ((int64_t)2 << 30) &&
-                hipMalloc(reinterpret_cast<void**>(&s->s3_colmax), (size_t)s->s3_colmax_cap * sizeof(float)) == hipSuccess) {
-                s->bytes += s->s3_colmax_cap * (int64_t)sizeof(float);
-            } else {
-                (void)hipGetLastError();
-                s->s3_colmax = nullptr; s->s3_colmax_cap = 0;
-            }
+            if (s->s3_colmax_cap * (int64_t)sizeof(float) > ((int64_t)2 << 30) ||
+                !ws_alloc_optional(s, &s->s3_colmax, (size_t)s->s3_colmax_cap, WS_FF))       // float column maxima
+                s->s3_colmax_cap = 0;
         }
     }
-    {
-        int32_t* p = nullptr;
-        rc = ws_alloc(s, &p, 2 * B + FLMR_FAST_HDR);
-        if (rc) { flmr_searcher_destroy(s); return rc; }
-        s->cand_fast = p;
-        FLMR_HIP(hipMemset(s->cand_fast, 0, (2 * B + FLMR_FAST_HDR) * sizeof(int32_t)));
-    }
+    // (plan words and key counters, written for every query of a batch before they are read; zeroed once here as before)
+    WS(cand_fast, 2 * B + FLMR_FAST_HDR, WS_ZERO);
+#undef WS
+    FLMR_HIP(hipMemset(s->cand_fast, 0, (2 * B + FLMR_FAST_HDR) * sizeof(int32_t)));
     FLMR_HIP(hipMemset(s->overflow, 0, 4 * sizeof(int32_t)));
     FLMR_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->status_host), 4 * sizeof(int32_t), hipHostMallocDefault));
     s->status_host[0] = s->status_host[1] = s->status_host[2] = s->status_host[3] = 0;
@@ -239,10 +282,7 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
 
 extern "C" int flmr_searcher_destroy(flmr_searcher_t* s) {
     if (!s) return FLMR_OK;
-    void* ptrs[] = {s->cs, s->rows, s->idx_prefix, s->idx_bits, s->part_val, s->part_idx, s->cells, s->ncell, s->bitmap, s->cand, s->cand_count,
-                    s->keys1, s->s1_pids, s->s1_count, s->keys2, s->s2_pids, s->s2_count, s->keys3, s->doc_scores,
-                    s->overflow, s->q_lens_ws, s->q_hi, s->q_lo, s->q_err, s->q_err_sum, s->s2_band, s->s2_band_count, s->s2_need, s->s2_def, s->keys2b, s->hit_bits, s->hit_valid, s->q3_hi, s->q3_lo, s->qual, s->nqual, s->chunk_cnt, s->chunk_hits, s->cand_hit, s->key_count, s->s1_slot, s->s2_slot, s->s2_part, s->s3_desc, s->s3_wbeg, s->s3_colmax, s->cand_fast, s->s1d_mode, s->s1d_band, s->s1d_band_count, s->s1d_err, s->s1d_in_count, s->s1d_scan_skip, s->row_ovf, s->s1d_any};
-    for (void* p : ptrs) (void)hipFree(p);
+    for (int i = 0; i < s->nws; i++) (void)hipFree(s->ws[i].ptr);
     if (s->status_host) (void)hipHostFree(s->status_host);
     if (s->status_ev) (void)hipEventDestroy(s->status_ev);
     for (int r = 0; r < FLMR_PROF_RING; r++)
@@ -506,7 +546,7 @@ static void plan_batch(run_ctx& c, bool whole_batch) {
 }
 
 static int prepare_ctx(run_ctx& c, flmr_searcher* s, const float* Q, const int32_t* q_lens, int32_t nqueries, int32_t nq,
-                       const flmr_search_params_t* p, flmr_stream_t stream, bool whole_batch = false) {
+                       const flmr_search_params_t* p, flmr_stream_t stream, bool whole_batch = false, bool first_phase = true) {
     if (!s || !Q) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     RUN(check_params(p));
     RUN(poll_status(s, false));
@@ -522,6 +562,15 @@ static int prepare_ctx(run_ctx& c, flmr_searcher* s, const float* Q, const int32
     c.stage = 0;
     if (s->profiling && s->ev_pending == FLMR_PROF_RING) RUN(fold_oldest(s));   // the ring is full: make room (waits)
     c.ev_set = (s->ev_first + s->ev_pending) % FLMR_PROF_RING;
+    c.sparse = sparse_path(s, ncol);
+    if (!c.sparse && !s->cs) {   // first batch that needs the whole K x ncol table per query: allocate it now (synchronous, once)
+        const size_t bytes = (size_t)s->max_queries * (size_t)ix->K * s->ncol_max * sizeof(float);
+        if (!ws_alloc_optional(s, &s->cs, bytes / sizeof(float), WS_FF))   // float scores (FLMR_TAP_CENTROID_SCORES reads the last batch's)
+            FLMR_FAIL(FLMR_ERR_NOMEM, "the full centroid-score table needs %.1f GB for %d queries (full-table mode: taps, centroids that are "
+                      "not fp16-representable, nq_cand > 32): create the searcher for fewer queries", bytes / 1e9, s->max_queries);
+    }
+    // test runs: nothing may be read from an earlier batch's workspace (before anything of this call is written into it)
+    if (s->opt.poison) RUN(ws_poison(s, nqueries, first_phase, c.st));
     if (q_lens) {  // kernels only ever see lengths inside [0, nq]; a violation is reported by the next status poll
         hipLaunchKernelGGL(sanitize_q_lens_kernel, dim3((nqueries + 255) / 256), dim3(256), 0, c.st, q_lens, nqueries, nq,
                            s->q_lens_ws, s->overflow + 1);
@@ -534,25 +583,6 @@ static int prepare_ctx(run_ctx& c, flmr_searcher* s, const float* Q, const int32
     const bool f16num = s->numerics == FLMR_NUMERICS_GPU_FP16;
     a0.thr = f16num ? f16_threshold(p->centroid_score_threshold) : p->centroid_score_threshold;
     a0.q_hi_only = f16num ? 1 : 0;
-    c.sparse = sparse_path(s, ncol);
-    if (!c.sparse && !s->cs) {   // first batch that needs the whole K x ncol table per query: allocate it now (synchronous, once)
-        const size_t bytes = (size_t)s->max_queries * (size_t)ix->K * s->ncol_max * sizeof(float);
-        if (hipMalloc(reinterpret_cast<void**>(&s->cs), bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            s->cs = nullptr;
-            FLMR_FAIL(FLMR_ERR_NOMEM, "the full centroid-score table needs %.1f GB for %d queries (full-table mode: taps, centroids that are "
-                      "not fp16-representable, nq_cand > 32): create the searcher for fewer queries", bytes / 1e9, s->max_queries);
-        }
-        s->bytes += (int64_t)bytes;
-    }
-    if (s->opt.poison) {   // test runs: nothing may be read from an earlier batch's workspace
-        FLMR_HIP(hipMemsetAsync(s->rows, 0xFF, (size_t)nqueries * s->row_cap * 32 * sizeof(float), c.st));
-        FLMR_HIP(hipMemsetAsync(s->idx_prefix, 0xFF, (size_t)nqueries * s->idx_words * sizeof(uint32_t), c.st));
-        FLMR_HIP(hipMemsetAsync(s->qual, 0xFF, (size_t)nqueries * s->qmax * sizeof(int32_t), c.st));
-        FLMR_HIP(hipMemsetAsync(s->keys1, 0xFF, (size_t)nqueries * s->cand_cap * sizeof(uint64_t), c.st));
-        FLMR_HIP(hipMemsetAsync(s->keys2, 0xFF, (size_t)nqueries * s->maxp.ndocs * sizeof(uint64_t), c.st));
-        FLMR_HIP(hipMemsetAsync(s->keys3, 0xFF, (size_t)nqueries * (s->maxp.ndocs / 4) * sizeof(uint64_t), c.st));
-    }
     a0.cs = c.sparse ? nullptr : s->cs; a0.idx_bits = s->idx_bits; a0.idx_words = s->idx_words;
     a0.part_val = s->part_val; a0.part_idx = s->part_idx;
     a0.cells = s->cells; a0.ncell = s->ncell; a0.max_cells = s->max_cells;
@@ -823,7 +853,7 @@ extern "C" int flmr_search_phase2(flmr_searcher_t* s, const float* Q, const int3
                                   flmr_stream_t stream) {
     if (!global_s1 || !out_keys) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     run_ctx c;
-    RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
+    RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream, false, false));
     if (n_in > p->ndocs) FLMR_FAIL(FLMR_ERR_INVALID, "n_in=%d > ndocs=%d", n_in, p->ndocs);
     RUN(flmr_launch_filter_local_keys(global_s1, nqueries, n_in, s->ix->pid_base, s->ix->num_passages, s->s1_pids, s->maxp.ndocs,
                                       s->s1_count, c.st, s->s1_slot));
@@ -839,7 +869,7 @@ extern "C" int flmr_search_phase3(flmr_searcher_t* s, const float* Q, const int3
                                   flmr_stream_t stream) {
     if (!global_s2 || !out_keys) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     run_ctx c;
-    RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream));
+    RUN(prepare_ctx(c, s, Q, q_lens, nqueries, nq, p, stream, false, false));
     if (n_in > p->ndocs / 4) FLMR_FAIL(FLMR_ERR_INVALID, "n_in=%d > ndocs/4=%d", n_in, p->ndocs / 4);
     RUN(flmr_launch_filter_local_keys(global_s2, nqueries, n_in, s->ix->pid_base, s->ix->num_passages, s->s2_pids,
                                       s->maxp.ndocs / 4, s->s2_count, c.st, s->s2_slot));

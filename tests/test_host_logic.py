@@ -505,3 +505,31 @@ def test_switch_values_are_parsed_and_checked():
     finally:
         for name in accepted:
             lib.flmr_set_option(name.encode(), None)
+
+
+def test_poison_switch_is_accepted_as_before():
+    """FLMR_POISON stays a plain flag of the unchanged switch table: flmr_set_option takes any non-empty value and clears it with
+    NULL or "", and a process started with it in the environment (any value, the empty one included) loads the library and sets /
+    clears every switch as usual -- what it now fills is the searcher's business (csrc/flmr_search.hip), not the parser's."""
+    import subprocess
+    import sys
+    lib = _native.load(require_device=False)
+    try:
+        for v in (b"1", b"0", b"yes"):
+            assert lib.flmr_set_option(b"FLMR_POISON", v) == 0, (v, lib.flmr_last_error())
+        assert lib.flmr_set_option(b"FLMR_POISON", b"") == 0 and lib.flmr_set_option(b"FLMR_POISON", None) == 0
+        assert lib.flmr_set_option(b"FLMR_POISON_ALL", b"1") == 1 and b"unknown option" in lib.flmr_last_error()
+    finally:
+        lib.flmr_set_option(b"FLMR_POISON", None)
+    src = open(os.path.join(ROOT, "retrieval-augmented-visual-question-answering_amd", "csrc", "flmr_index.hip")).read()
+    table = src[src.index("kOpts[O_COUNT]"):src.index("#undef N_")]
+    assert re.findall(r'\{"(FLMR_[A-Z0-9_]+)"', table) == [
+        "FLMR_S0_IMPL", "FLMR_FULL_TABLE", "FLMR_CAND_IMPL", "FLMR_S1_NO_HITMAP", "FLMR_S1_IMPL", "FLMR_S2_IMPL", "FLMR_S0_STAGED",
+        "FLMR_S3_NO_MULTIQ", "FLMR_S3_IMPL", "FLMR_SCORE_IMPL", "FLMR_POISON", "FLMR_ROW_CAP"]
+    code = ("import sys; sys.path.insert(0, %r); from ravqa_amd import _native as n; lib = n.load(require_device=False); "
+            "assert lib.flmr_set_option(b'FLMR_S1_IMPL', b'scan') == 0; assert lib.flmr_set_option(b'FLMR_S1_IMPL', b'narrow') == 1; "
+            "assert lib.flmr_set_option(b'FLMR_POISON', None) == 0; assert lib.flmr_set_option(b'FLMR_POISON', b'1') == 0; print('ok')" % ROOT)
+    for value in ("1", "0", ""):
+        env = dict(os.environ, FLMR_POISON=value)
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout.strip() == "ok", (value, r.stdout, r.stderr)
