@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FLMR_ABI_VERSION 7
+#define FLMR_ABI_VERSION 8
 
 typedef enum flmr_status {
     FLMR_OK = 0,
@@ -360,6 +360,36 @@ int flmr_colbert_maxsim_fwd(const float* Q, int32_t q_batch, int32_t nq, const f
 int flmr_colbert_maxsim_bwd(const float* Q, int32_t q_batch, int32_t nq, const float* D, int32_t B, int32_t Ld, int32_t dim,
                             int32_t cross, const int32_t* argmax, const float* grad_colmax, float* dQ, float* dD,
                             flmr_stream_t stream);
+
+/* Retrieve-and-rescore (the re-scoring of retrieved passages under autograd inside the RAG model's training step,
+ * src/models/rag/rag_model_blip.py:409-442): the GATHERED forms of flmr_colbert_maxsim_fwd / _bwd.  The documents are not an
+ * argument but rows of a device-resident passage store [npassages, Ld, dim] -- fp32 (FLMR_F32) or IEEE half bit patterns
+ * (FLMR_F16), 16-byte aligned -- with store_mask u8 [npassages, Ld] (1 = real token; NOT necessarily a prefix: the punctuation
+ * skiplist masks interior tokens, TPC/modeling/colbert.py:194-215).  Output row r = q * k + j scores query q of
+ * Q f32 [nqueries, nq, dim] against passage pids[q, j]; neither Q.repeat_interleave(k) nor store[pids] is materialised.
+ *
+ * flmr_maxsim_gather_fwd: out f32 [nqueries, k] and colmax f32 [nqueries, k, nq] (each nullable), argmax i32 [nqueries, k, nq].
+ *   Arithmetic, -9999 padding, no zero clamp, lowest-token tie rule and argmax = -1 for a padded winner are those of
+ *   flmr_colbert_maxsim_fwd, and for an fp32 store the three outputs are bit-identical to that entry point run on the
+ *   materialised operands.  An EMPTY SLOT (pid < 0, what flmr_search_batch writes past counts[q]) is an all-padded document:
+ *   out = nq x -9999 summed in the kernel's order, argmax = -1.  A pid >= npassages is the caller's error (the entry point cannot
+ *   see device values; callers validate); the kernels treat it as an empty slot rather than read out of bounds.
+ *   An fp16 store value has a zero low part in the fp16 split, so that product is not issued (two MFMAs per tile instead of
+ *   three, half the bytes per token row); the results are bit-identical to the fp32 store holding the widened values.
+ * flmr_maxsim_gather_bwd: dQ f32 [nqueries, nq, dim] alone (the store is a constant of training, there is no dD):
+ *     dQ[q, i] = sum over j ASCENDING of G[q * k + j, i] * store[pids[q, j], argmax[q * k + j, i]], skipped where argmax < 0;
+ *   fixed order, no floating-point atomics: two calls give the same bits.
+ * Both enqueue on `stream`, use no workspace and do not synchronise.  dim != 128 -> FLMR_ERR_UNSUPPORTED; nq * 8 > 64 KiB ->
+ * FLMR_ERR_UNSUPPORTED; NULL pointers, negative sizes, an unknown store_dtype, a misaligned Q / store -> FLMR_ERR_INVALID;
+ * nqueries * k == 0 -> FLMR_OK and nothing is launched (dQ is then the caller's to zero). */
+#define FLMR_F32 0
+#define FLMR_F16 1
+int flmr_maxsim_gather_fwd(const float* Q, int32_t nqueries, int32_t nq, const void* store, int32_t store_dtype,
+                           const uint8_t* store_mask, int32_t npassages, int32_t Ld, int32_t dim, const int32_t* pids, int32_t k,
+                           float* out, float* colmax, int32_t* argmax, flmr_stream_t stream);
+int flmr_maxsim_gather_bwd(const void* store, int32_t store_dtype, int32_t npassages, int32_t Ld, int32_t dim, const int32_t* pids,
+                           int32_t nqueries, int32_t k, int32_t nq, const int32_t* argmax, const float* grad_colmax, float* dQ,
+                           flmr_stream_t stream);
 
 /* Merge per-shard top-k lists after the RCCL all-gather: scores f32[nshards, nqueries, k],
  * pids i32[nshards, nqueries, k] (-1 = empty) -> global top-k per query in descending (score,pid) order. */

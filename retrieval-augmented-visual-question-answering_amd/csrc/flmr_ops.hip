@@ -295,6 +295,8 @@ __global__ __launch_bounds__(256) void score_split_q(const float* Q, int rows, i
 // fp32 column maximum of the plain instantiation and whose low word makes ties go to the LOWEST token, as torch's max(dim)
 // does under autograd.  That instantiation reads fp32 Q and splits it while staging (the same hi/lo values score_split_q
 // writes), so it needs no workspace and no host synchronisation.
+// TWIN: maxsim_gather_fwd_kernel (flmr_rescore.hip) is this instantiation with the document taken from a passage store by pid;
+// a fix to the tile walk, the key or the tie rule here must be made there too (tests/test_rag_rescore_gpu.py asserts bit-identity).
 template <bool ARGMAX>
 __global__ __launch_bounds__(256, 2) void colbert_score_padded_mfma_kernel(const _Float16* __restrict__ q_hi,
                                                                            const _Float16* __restrict__ q_lo,

@@ -164,6 +164,58 @@ def colbert_maxsim_bwd(Q, D_padded, argmax, grad_colmax, cross=False, need_dQ=Tr
     return dQ, dD
 
 
+def _store_dtype(store):
+    if store.dtype == torch.float16:
+        return _native.FLMR_F16
+    if store.dtype == torch.float32:
+        return _native.FLMR_F32
+    raise TypeError(f"the passage store is fp32 or fp16, not {store.dtype}")
+
+
+def maxsim_gather_fwd(Q, store, store_mask, pids, want_out=True, want_colmax=False):
+    """The gathered autograd forward (flmr_maxsim_gather_fwd): fp32 CUDA Q [n, Nq, 128], a resident store [P, Ld, 128] (fp32 or
+    fp16, used in place: never copied or widened), store_mask [P, Ld] (uint8 / bool), pids i32 [n, k] (< 0 = empty slot) ->
+    (out f32 [n, k] | None, colmax f32 [n, k, Nq] | None, argmax i32 [n, k, Nq]).  Row (q, j) is query q against passage
+    pids[q, j]; an fp32 store gives the bits of colbert_maxsim_fwd on Q.repeat_interleave(k) and store[pids], an fp16 store the
+    bits of the fp32 store of the widened values.  pids >= P are the caller's error (rag.PassageEmbeddingStore validates).
+    Enqueued on the current stream, no synchronisation."""
+    lib = _native.load()
+    Qd, pd = _d(Q, torch.float32), _d(pids, torch.int32)
+    sd = store.to("cuda").contiguous()
+    P, Ld, dim = sd.shape
+    md = torch.as_tensor(store_mask).reshape(P, Ld)
+    md = _d(md) if md.dtype == torch.uint8 else _d(md, torch.bool).view(torch.uint8)   # (a resident uint8 mask is used in place)
+    n, nq = Qd.size(0), Qd.size(1)
+    assert pd.dim() == 2 and pd.size(0) == n, (tuple(pd.shape), n)
+    k = pd.size(1)
+    out = torch.empty((n, k), dtype=torch.float32, device="cuda") if want_out else None
+    colmax = torch.empty((n, k, nq), dtype=torch.float32, device="cuda") if want_colmax else None
+    argmax = torch.empty((n, k, nq), dtype=torch.int32, device="cuda")
+    if n * k == 0:
+        return out, colmax, argmax   # (empty tensors may have NULL data pointers, which the C ABI rejects)
+    _native.check(lib.flmr_maxsim_gather_fwd(_p(Qd), n, nq, _p(sd), _store_dtype(sd), _p(md), P, Ld, dim, _p(pd), k, _p(out),
+                                             _p(colmax), _p(argmax), _native.stream_ptr()))
+    return out, colmax, argmax
+
+
+def maxsim_gather_bwd(store, pids, argmax, grad_colmax):
+    """The gathered autograd backward (flmr_maxsim_gather_bwd): the forward's argmax and G = dL/dcolmax, both [n, k, Nq] ->
+    dQ f32 [n, Nq, 128], each (q, i) summed over the query's k passages in ascending j.  There is no store gradient.
+    Deterministic; enqueued on the current stream."""
+    lib = _native.load()
+    sd = store.to("cuda").contiguous()
+    P, Ld, dim = sd.shape
+    pd, am, G = _d(pids, torch.int32), _d(argmax, torch.int32), _d(grad_colmax, torch.float32)
+    n, k, nq = am.shape
+    assert tuple(pd.shape) == (n, k) and G.shape == am.shape, (tuple(pd.shape), tuple(am.shape), tuple(G.shape))
+    if n * k == 0:
+        return torch.zeros((n, nq, dim), dtype=torch.float32, device="cuda")
+    dQ = torch.empty((n, nq, dim), dtype=torch.float32, device="cuda")
+    _native.check(lib.flmr_maxsim_gather_bwd(_p(sd), _store_dtype(sd), P, Ld, dim, _p(pd), n, k, nq, _p(am), _p(G), _p(dQ),
+                                             _native.stream_ptr()))
+    return dQ
+
+
 def merge_topk(scores, pids):
     """scores f32 / pids i32 [nshards, nqueries, k] (CUDA) -> merged (scores, pids, counts) [nqueries, k]."""
     lib = _native.load()

@@ -1,0 +1,198 @@
+"""Retrieve-and-rescore for RAG training: search -> gather -> differentiable score, all on the device.
+
+Inside a training step `RagModelForBlip.main_retrieve` (src/models/rag/rag_model_blip.py:339-443) encodes the questions,
+searches the index with the detached embeddings (:397), then -- per query, in a Python loop -- pulls the retrieved passages'
+uncompressed padded embeddings out of a host dict loaded from a pickle (:303-311, :419-428: `torch.Tensor(...)` per passage,
+`stack`, `.to(device)`) and re-scores them under autograd with `question_encoder.score(Q_duplicated, D, mask)` (:430-435).
+Here the dict is a `PassageEmbeddingStore` resident in HBM, and `retrieve_and_rescore` runs the three steps without a host
+round trip: `IndexScorer.search_batch` hands over device pids, and `flmr_maxsim_gather_fwd / _bwd` read the store's rows by
+pid, so neither `Q_duplicated` [B * k, Nq, 128] nor a padded document copy [B * k, Ld, 128] is ever built.
+
+    store = PassageEmbeddingStore.from_reference_file(embedding_path)          # once, replaces :303-311
+    r = searcher.retrieve_and_rescore(question_hidden_states, store, n_docs)   # per step, replaces :397-443
+    doc_scores, ids = r.doc_scores, r.passage_ids                              # [B, n_docs] with grad to the encoder
+
+Limits: dim 128; one padded length Ld for the whole store; the store must fit HBM (110 k passages x 512 x 128 fp16 = 14.4 GB).
+Re-scoring from the compressed index for corpora whose uncompressed embeddings do not fit is out of scope.
+"""
+import pickle
+
+import numpy as np
+import torch
+
+from . import scoring
+
+
+def _rows(x, i0, i1):
+    """Passages i0..i1 of a tensor / array / list of per-passage arrays as one CPU or device tensor [n, ...]."""
+    if isinstance(x, (list, tuple)):
+        return torch.stack([torch.as_tensor(np.asarray(a)) if not torch.is_tensor(a) else a for a in x[i0:i1]])
+    return torch.as_tensor(x[i0:i1])
+
+
+class PassageEmbeddingStore:
+    """The device-resident replacement of the RAG model's `self.item_embeddings` dict (rag_model_blip.py:303-311):
+    `embeddings` [P, Ld, 128] fp16 or fp32, `mask` uint8 [P, Ld] (1 = real token; interior holes allowed), and the reference's
+    `passage_index2id`.  Built once; `score` re-scores device pids under autograd without copying a row."""
+
+    def __init__(self, embeddings, mask, passage_index2id=None):
+        assert embeddings.dim() == 3 and embeddings.dtype in (torch.float16, torch.float32), (embeddings.shape, embeddings.dtype)
+        assert mask.shape == embeddings.shape[:2] and mask.dtype == torch.uint8, (mask.shape, mask.dtype)
+        self.embeddings, self.mask, self.passage_index2id = embeddings, mask, passage_index2id
+
+    @classmethod
+    def from_padded(cls, item_embeddings, item_embedding_mask, passage_index2id=None, dtype="auto", device="cuda", chunk=1024):
+        """item_embeddings: a tensor / array [P, Ld, 128] or the reference's list of P per-passage arrays [Ld, 128];
+        item_embedding_mask: [P, Ld] or [P, Ld, 1] (what `doc(..., keep_dims="return_mask")` yields, colbert.py:194-215), or a
+        list of per-passage [Ld] / [Ld, 1] arrays.  Uploaded `chunk` passages at a time, so the host never holds a second copy.
+
+        dtype="auto" keeps fp16 when EVERY value survives x.half().float() == x (checked chunk by chunk on the device: the
+        embeddings of an encoder that ran under autocast do) and fp32 otherwise -- scores are the same bits either way.
+        dtype="float16" FORCES rounding to half: the store is half the size, and scores then differ from those of the fp32
+        embeddings by the rounding of every document value (~2^-11 relative).  dtype="float32" never rounds.
+        Device memory while building: "auto" starts in fp16 and, at the first chunk holding a value half cannot represent,
+        allocates the fp32 store beside it and widens what is there, so the peak is 1.5x the final fp32 store (110 k passages x
+        512 tokens: 14.4 GB + 28.8 GB).  For embeddings known not to be half-exact pass dtype="float32"."""
+        if dtype not in ("auto", "float16", "float32"):
+            raise ValueError(f"dtype must be 'auto', 'float16' or 'float32', got {dtype!r}")
+        P = len(item_embeddings)
+        if len(item_embedding_mask) != P:
+            raise ValueError(f"{P} passages but {len(item_embedding_mask)} masks")
+        if P == 0:
+            raise ValueError("an empty passage store")
+        first = _rows(item_embeddings, 0, 1)
+        if first.dim() != 3 or first.size(-1) != 128:
+            raise ValueError(f"passages must be [Ld, 128], got {tuple(first.shape[1:])}")
+        Ld = first.size(1)
+        half = dtype != "float32"
+        emb = torch.empty((P, Ld, 128), dtype=torch.float16 if half else torch.float32, device=device)
+        mask = torch.empty((P, Ld), dtype=torch.uint8, device=device)
+        for i0 in range(0, P, max(int(chunk), 1)):
+            i1 = min(i0 + max(int(chunk), 1), P)
+            x = _rows(item_embeddings, i0, i1)
+            if tuple(x.shape[1:]) != (Ld, 128):
+                raise ValueError(f"passages {i0}..{i1}: {tuple(x.shape[1:])}, the store is padded to one length ({Ld}, 128)")
+            m = _rows(item_embedding_mask, i0, i1).reshape(i1 - i0, -1)
+            if m.size(1) != Ld:
+                raise ValueError(f"masks {i0}..{i1}: {m.size(1)} tokens, embeddings have {Ld}")
+            x = x.to(device)
+            mask[i0:i1] = (m.to(device) != 0).to(torch.uint8)
+            if x.dtype == torch.float16 and half:
+                emb[i0:i1] = x
+                continue
+            x = x.float()
+            if half and dtype == "auto" and not torch.equal(x.half().float(), x):
+                # a value that half cannot hold: the store becomes fp32 (what is already there was exact, so widening it is too)
+                wide = torch.empty((P, Ld, 128), dtype=torch.float32, device=device)
+                wide[:i0] = emb[:i0]
+                emb, half = wide, False
+            emb[i0:i1] = x   # (rounds only under dtype="float16")
+        return cls(emb, mask, passage_index2id)
+
+    @classmethod
+    def from_reference_file(cls, path, dtype="auto", device="cuda", chunk=1024):
+        """The pickle the RAG model reads (rag_model_blip.py:305-311): a dict with "item_embeddings" and "item_embedding_mask",
+        two parallel lists of per-passage arrays, and the dict "passage_index2id"."""
+        with open(path, "rb") as f:
+            data = pickle.load(f)
+        return cls.from_padded(data["item_embeddings"], data["item_embedding_mask"], data.get("passage_index2id"), dtype=dtype,
+                               device=device, chunk=chunk)
+
+    def __len__(self):
+        return self.embeddings.size(0)
+
+    @property
+    def dtype(self):
+        return self.embeddings.dtype
+
+    @property
+    def device(self):
+        return self.embeddings.device
+
+    @property
+    def nbytes(self):
+        return self.embeddings.numel() * self.embeddings.element_size() + self.mask.numel()
+
+    def _checked(self, pids):
+        pids = torch.as_tensor(pids).to(self.device)
+        if pids.numel() and int(pids.max()) >= len(self):   # one device reduction; < 0 is an empty slot
+            raise IndexError(f"pid {int(pids.max())} is outside the store's {len(self)} passages")
+        return pids
+
+    def score(self, Q, pids, config=None):
+        """Q [n, Nq, 128] (fp32 / fp16 / bf16, widened exactly), pids [n, k] (< 0 = empty slot, scored as an all-padded document)
+        -> f32 [n, k], differentiable in Q; dQ comes back in Q's dtype.  'flipr' reduces the differentiable column maxima with
+        scoring.reduce_colmax.  Raises IndexError for a pid >= len(self) before anything is launched: that check is one device
+        reduction whose result the host waits for, so every call synchronises with the device once."""
+        pids = self._checked(pids)
+        return scoring.maxsim_gather_differentiable(Q.to(self.device), self.embeddings, self.mask, pids, config)
+
+    def lookup(self, pids, dtype=torch.float32):
+        """The padded copy, for callers that do want it: pids [...] -> (D [pids.numel(), Ld, 128] in `dtype`, mask bool
+        [pids.numel(), Ld]); an empty slot (pid < 0) is a zero document with an all-zero mask."""
+        flat = self._checked(pids).reshape(-1).long()
+        live = flat >= 0
+        idx = flat.clamp(min=0)
+        D = self.embeddings[idx].to(dtype) * live.view(-1, 1, 1).to(dtype)
+        return D, self.mask[idx].bool() & live.view(-1, 1)
+
+
+class RescoreResult:
+    """What `retrieve_and_rescore` returns: pids i32 [B, n_docs] (-1 = empty slot), doc_scores f32 [B, n_docs] with a gradient
+    to Q, the index's own scores [B, n_docs] (no gradient) and counts i32 [B] = the filled slots of each row, all on the
+    device; `passage_ids` maps the pids through the store's passage_index2id on the host when it is first read."""
+
+    def __init__(self, pids, doc_scores, index_scores, counts, store):
+        self.pids, self.doc_scores, self.index_scores, self.counts = pids, doc_scores, index_scores, counts
+        self._store, self._passage_ids = store, None
+
+    @property
+    def passage_ids(self):
+        if self._passage_ids is None:
+            m = self._store.passage_index2id
+            rows = self.pids.cpu().tolist()
+            self._passage_ids = [[None if p < 0 else (m[p] if m is not None else p) for p in row] for row in rows]
+        return self._passage_ids
+
+
+def retrieve_and_rescore(searcher, store, Q, n_docs, n_docs_retrieve=None, generator=None, config=None):
+    """One training step's retrieval (rag_model_blip.py:392-443): search the index with Q.detach() on the device, then re-score
+    the retrieved passages from `store` under autograd.  Q [B, Nq, 128] (with grad) -> RescoreResult.  `config` is the scoring
+    model's ColBERT config (its `interaction`; None = 'colbert'), as for scoring.colbert_score_differentiable.
+
+    The search is the batched branch of `Searcher._search_all_Q` (the searcher's k-policy, sticky on its config;
+    kk = min(k, ndocs // 4); the checked batch where the ranker has one), so the pids are those `_search_all_Q` ranks, in rank
+    order.  As the reference does for n_docs < 5 (:392-395, :412-413), max(n_docs, 5) passages are retrieved (or
+    `n_docs_retrieve`) and n_docs of them kept, chosen uniformly without replacement per query -- here by `generator` (a torch
+    generator of the store's device) and with the kept ones left in rank order, which `random.sample` does not guarantee; the
+    reference draws from Python's unseeded `random`, so there is no sequence to reproduce.  A query for which the index returned
+    fewer than n_docs passages keeps them all and has empty slots (pid -1, score of an all-padded document, no gradient) where
+    the reference's `random.sample` / `np.array` would raise."""
+    n_docs = int(n_docs)
+    if n_docs < 1:
+        raise ValueError(f"n_docs = {n_docs}")
+    k = int(n_docs_retrieve) if n_docs_retrieve is not None else max(n_docs, 5)
+    if k < n_docs:
+        raise ValueError(f"n_docs_retrieve = {k} < n_docs = {n_docs}")
+    searcher._apply_k_policy(k)
+    c, ranker = searcher.config, searcher.ranker
+    kk = min(k, max(c.ndocs // 4, 1))
+    search = getattr(ranker, "search_batch_checked", None) or ranker.search_batch
+    pids, scores, counts = search(Q.detach(), kk, c.ncells, c.centroid_score_threshold, c.ndocs, c.query_maxlen)
+    if not hasattr(ranker, "search_batch_checked") and hasattr(ranker, "check"):
+        ranker.check()
+    pids, scores, counts = pids.to(store.device), scores.to(store.device), counts.to(store.device)
+    slot = torch.arange(kk, device=store.device).unsqueeze(0)
+    pids = torch.where(slot < counts.unsqueeze(1), pids, torch.full_like(pids, -1))
+    if n_docs < kk:
+        # a uniform draw without replacement among each row's filled slots: random keys, empty slots last, the n_docs smallest
+        key = torch.rand(pids.shape, generator=generator, device=store.device).masked_fill(pids < 0, 2.0)
+        keep = key.argsort(dim=1)[:, :n_docs].sort(dim=1).values
+        pids, scores = pids.gather(1, keep), scores.gather(1, keep)
+    elif n_docs > kk:   # (the policy's ndocs // 4 bound: fewer columns than asked for)
+        pad = (pids.size(0), n_docs - kk)
+        pids = torch.cat([pids, pids.new_full(pad, -1)], dim=1)
+        scores = torch.cat([scores, scores.new_zeros(pad)], dim=1)
+    counts = (pids >= 0).sum(dim=1).to(torch.int32)
+    doc_scores = store.score(Q, pids.contiguous(), config)
+    return RescoreResult(pids, doc_scores, scores, counts, store)

@@ -7,7 +7,10 @@ silently computing without a graph.  The score under autograd -- RA-VQA's re-sco
 (src/models/rag/rag_model_blip.py:430-435) and the in-batch-negative loss of retriever training (`compute_ib_loss_new`,
 colbert.py:82-113) -- goes through `colbert_score_differentiable`, `colbert_score_cross_differentiable` and
 `in_batch_negative_loss`: the HIP forward records the winning token of every column and the HIP backward gathers the
-gradients from it (flmr_colbert_maxsim_fwd / _bwd), so the [B, Ld, Nq] score tensor is never materialised.
+gradients from it (flmr_colbert_maxsim_fwd / _bwd), so the [B, Ld, Nq] score tensor is never materialised.  Where the
+documents are passages of a device-resident store picked by pid -- the RAG model's re-scoring of what it has just retrieved --
+`maxsim_gather_differentiable` (rag.PassageEmbeddingStore.score) does the same without building the padded document copy or the
+duplicated queries (flmr_maxsim_gather_fwd / _bwd).
 """
 import torch
 
@@ -96,6 +99,46 @@ def _maxsim(Q, D_padded, D_mask, config, cross):
     return _MaxSim.apply(Q, D_padded, D_mask, cross, False)
 
 
+class _MaxSimGather(torch.autograd.Function):
+    """_MaxSim whose documents are rows of a resident passage store picked by pid: row (q, j) is query q against passage
+    pids[q, j] (< 0: an empty slot, an all-padded document).  Saves (Q, pids, argmax) and the store by reference; the store is a
+    constant of training, so Q is the only input with a gradient.  Returns [n, k] sums or [n, k, Nq] column maxima."""
+
+    @staticmethod
+    def forward(ctx, Q, store, store_mask, pids, want_colmax):
+        out, colmax, argmax = ops.maxsim_gather_fwd(Q.detach().float(), store, store_mask, pids, want_out=not want_colmax,
+                                                    want_colmax=want_colmax)
+        ctx.save_for_backward(Q, store, pids, argmax)
+        ctx.want_colmax = want_colmax
+        return colmax if want_colmax else out
+
+    @staticmethod
+    def backward(ctx, grad):
+        Q, store, pids, argmax = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        G = grad.float() if ctx.want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)
+        dQ = ops.maxsim_gather_bwd(store, pids, argmax, G.contiguous())
+        return dQ.to(Q.dtype), None, None, None, None
+
+
+def maxsim_gather_differentiable(Q, store, store_mask, pids, config=None):
+    """Re-scoring of retrieved passages under autograd (rag_model_blip.py:430-435 for a whole batch): Q [n, Nq, 128], a resident
+    store [P, Ld, 128] (fp32 / fp16) + mask [P, Ld], pids i32 [n, k] -> f32 [n, k], differentiable in Q only.  Values are those
+    of colbert_score_differentiable(Q.repeat_interleave(k, 0), store[pids], mask[pids]); pids must be < P (the caller checks:
+    rag.PassageEmbeddingStore.score does)."""
+    if Q.dim() != 3 or store.dim() != 3 or Q.size(-1) != store.size(-1) or pids.dim() != 2 or pids.size(0) != Q.size(0):
+        raise ValueError(f"Q {tuple(Q.shape)} / store {tuple(store.shape)} / pids {tuple(pids.shape)}: expected [n, Nq, d], "
+                         "[P, Ld, d] and [n, k]")
+    if store.requires_grad:
+        raise RuntimeError("the passage store is a constant of training: there is no store gradient (detach it)")
+    Q, pids = Q.to(_device), pids.to(device=_device, dtype=torch.int32)
+    if _interaction(config) == "flipr":
+        colmax = _MaxSimGather.apply(Q, store, store_mask, pids, True)
+        return reduce_colmax(colmax.flatten(0, 1), config).reshape(pids.shape)
+    return _MaxSimGather.apply(Q, store, store_mask, pids, False)
+
+
 def colbert_score_differentiable(Q, D_padded, D_mask, config=None):
     """colbert_score (colbert.py:268-286) under autograd: Q [1|B, Nq, 128], D [B, Ld, 128] -> f32 [B] on the device, with
     dQ / dD equal to what torch's autograd gives the reference expression.  fp16 / bf16 inputs are widened exactly to fp32;
@@ -144,7 +187,8 @@ class FLMRScoringHead:
     """`score(Q, D_padded, D_mask)` with the semantics the four FLMR model classes inherit from ColBERT.score
     (colbert.py:217-224, similarity == 'cosine' path): exhaustive-search and RAG re-scoring callers
     (src/executors/FLMR_executor.py:833, src/models/rag/rag_model_blip.py:435) can bind this in place of the
-    torch expression when gradients are off."""
+    torch expression when gradients are off.  When they are on -- the RAG model's training step -- the re-scoring goes through
+    `rag.retrieve_and_rescore` / `rag.PassageEmbeddingStore.score`, which reads the retrieved passages from a device store."""
 
     def score(self, Q, D_padded, D_mask):
         return colbert_score(Q, D_padded, D_mask)
