@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FLMR_ABI_VERSION 8
+#define FLMR_ABI_VERSION 9
 
 typedef enum flmr_status {
     FLMR_OK = 0,
@@ -390,6 +390,29 @@ int flmr_maxsim_gather_fwd(const float* Q, int32_t nqueries, int32_t nq, const v
 int flmr_maxsim_gather_bwd(const void* store, int32_t store_dtype, int32_t npassages, int32_t Ld, int32_t dim, const int32_t* pids,
                            int32_t nqueries, int32_t k, int32_t nq, const int32_t* argmax, const float* grad_colmax, float* dQ,
                            flmr_stream_t stream);
+
+/* Retrieve-and-rescore from the COMPRESSED INDEX: the same pair with the resident flmr_index_t as the document source, for
+ * corpora whose uncompressed embeddings do not fit a resident store (nothing is kept beyond the index: no padded length, no mask,
+ * no second copy).  Token t of a passage is the row the reference's CPU branch forms (TPC/search/index_storage.py:160-173:
+ * decompress_residuals_cpp, then F.normalize), in fp32:
+ *     x_t = centroids[codes[t]] + (the bucket weights of its residual bytes),   D_t = x_t / max(||x_t||, 1e-12)
+ * whatever numerics mode a searcher on the index runs, and also for an index whose centroids are not fp16-representable.
+ * pids i32 [nqueries, k] are those flmr_search_batch returns for this index: each is taken relative to the index's pid_base; a
+ * pid < 0, a pid outside [pid_base, pid_base + num_passages) and a passage of length 0 are all-padded documents (every column
+ * -9999, argmax -1).
+ * flmr_maxsim_index_fwd: out f32 [nqueries, k] and colmax f32 [nqueries, k, nq] (each nullable), argmax i32 [nqueries, k, nq]:
+ *     colmax[q, j, i] = max over the tokens t of passage pids[q, j] of Q[q, i] . D_t   (no zero clamp: the training-side
+ *     colbert_score, equal to the search's score of the passage wherever no column maximum is negative),
+ *     out[q, j] = sum_i colmax[q, j, i],   argmax = the lowest token (relative to the passage) holding the maximum.
+ * flmr_maxsim_index_bwd: dQ[q, i] = sum over j ASCENDING of G[q * k + j, i] * D[pids[q, j], argmax[q * k + j, i]], skipped where
+ *   argmax < 0; the winner rows are decoded on the fly; fixed order, no floating-point atomics: two calls give the same bits.
+ * Both enqueue on `stream`, use no workspace and do not synchronise.  dim != 128 -> FLMR_ERR_UNSUPPORTED; nq * 8 > 64 KiB ->
+ * FLMR_ERR_UNSUPPORTED; NULL pointers, negative sizes, a misaligned Q -> FLMR_ERR_INVALID; nqueries * k == 0 -> FLMR_OK and
+ * nothing is launched (dQ is then the caller's to zero). */
+int flmr_maxsim_index_fwd(const flmr_index_t* index, const float* Q, int32_t nqueries, int32_t nq, const int32_t* pids, int32_t k,
+                          float* out, float* colmax, int32_t* argmax, flmr_stream_t stream);
+int flmr_maxsim_index_bwd(const flmr_index_t* index, const int32_t* pids, int32_t nqueries, int32_t k, int32_t nq,
+                          const int32_t* argmax, const float* grad_colmax, float* dQ, flmr_stream_t stream);
 
 /* Merge per-shard top-k lists after the RCCL all-gather: scores f32[nshards, nqueries, k],
  * pids i32[nshards, nqueries, k] (-1 = empty) -> global top-k per query in descending (score,pid) order. */

@@ -216,6 +216,45 @@ def maxsim_gather_bwd(store, pids, argmax, grad_colmax):
     return dQ
 
 
+def maxsim_index_fwd(device_index, Q, pids, want_out=True, want_colmax=False):
+    """The gathered autograd forward with the compressed index as the document source (flmr_maxsim_index_fwd): a resident
+    index.DeviceIndex, fp32 CUDA Q [n, Nq, 128], pids i32 [n, k] as search_batch returns them (< 0, outside the index or a
+    passage of length 0: an all-padded document) -> (out f32 [n, k] | None, colmax f32 [n, k, Nq] | None, argmax i32 [n, k, Nq]).
+    Row (q, j) is query q against the decompressed, normalised tokens of passage pids[q, j] (index_storage.py:160-173), -9999
+    padding, no zero clamp.  Enqueued on the current stream, no synchronisation."""
+    lib = _native.load()
+    Qd, pd = _d(Q, torch.float32), _d(pids, torch.int32)
+    n, nq = Qd.size(0), Qd.size(1)
+    assert Qd.dim() == 3 and pd.dim() == 2 and pd.size(0) == n, (tuple(Qd.shape), tuple(pd.shape))
+    k = pd.size(1)
+    out = torch.empty((n, k), dtype=torch.float32, device="cuda") if want_out else None
+    colmax = torch.empty((n, k, nq), dtype=torch.float32, device="cuda") if want_colmax else None
+    argmax = torch.empty((n, k, nq), dtype=torch.int32, device="cuda")
+    if n * k == 0:
+        return out, colmax, argmax   # (empty tensors may have NULL data pointers, which the C ABI rejects)
+    if Qd.size(2) != device_index.arrays.dim:
+        raise ValueError(f"Q has dim {Qd.size(2)}, the index {device_index.arrays.dim}")
+    _native.check(lib.flmr_maxsim_index_fwd(device_index.handle, _p(Qd), n, nq, _p(pd), k, _p(out), _p(colmax), _p(argmax),
+                                            _native.stream_ptr()))
+    return out, colmax, argmax
+
+
+def maxsim_index_bwd(device_index, pids, argmax, grad_colmax):
+    """The backward of maxsim_index_fwd (flmr_maxsim_index_bwd): the forward's argmax and G = dL/dcolmax, both [n, k, Nq] ->
+    dQ f32 [n, Nq, 128], each (q, i) summed over the query's k passages in ascending j, the winner rows decoded from the index.
+    The index is a constant: there is no other gradient.  Deterministic; enqueued on the current stream."""
+    lib = _native.load()
+    pd, am, G = _d(pids, torch.int32), _d(argmax, torch.int32), _d(grad_colmax, torch.float32)
+    n, k, nq = am.shape
+    assert tuple(pd.shape) == (n, k) and G.shape == am.shape, (tuple(pd.shape), tuple(am.shape), tuple(G.shape))
+    dim = device_index.arrays.dim
+    if n * k == 0:
+        return torch.zeros((n, nq, dim), dtype=torch.float32, device="cuda")
+    dQ = torch.empty((n, nq, dim), dtype=torch.float32, device="cuda")
+    _native.check(lib.flmr_maxsim_index_bwd(device_index.handle, _p(pd), n, k, nq, _p(am), _p(G), _p(dQ), _native.stream_ptr()))
+    return dQ
+
+
 def merge_topk(scores, pids):
     """scores f32 / pids i32 [nshards, nqueries, k] (CUDA) -> merged (scores, pids, counts) [nqueries, k]."""
     lib = _native.load()

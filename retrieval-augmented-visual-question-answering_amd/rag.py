@@ -12,8 +12,13 @@ pid, so neither `Q_duplicated` [B * k, Nq, 128] nor a padded document copy [B * 
     r = searcher.retrieve_and_rescore(question_hidden_states, store, n_docs)   # per step, replaces :397-443
     doc_scores, ids = r.doc_scores, r.passage_ids                              # [B, n_docs] with grad to the encoder
 
-Limits: dim 128; one padded length Ld for the whole store; the store must fit HBM (110 k passages x 512 x 128 fp16 = 14.4 GB).
-Re-scoring from the compressed index for corpora whose uncompressed embeddings do not fit is out of scope.
+Limits of the resident store: dim 128; one padded length Ld for the whole store; it must fit HBM (110 k passages x 512 x 128
+fp16 = 14.4 GB).  A corpus too large for that -- the 1 M and 6 M passage corpora need 130 GB to 800 GB -- is re-scored from the
+compressed index the searcher already holds: `CompressedPassageStore` (what `retrieve_and_rescore(Q, None, n_docs)` builds)
+scores through flmr_maxsim_index_fwd / _bwd, which decode the passages' tokens inside the kernels, so there is no pickle, no
+second copy of the corpus and no common padded length.  Out of scope there: a gradient to the documents, the
+gpu-fp16 numerics mode (the re-score is always the fp32 CPU-path definition), ShardedSearcher, dim != 128, the prediction-file
+reader and the marginalised loss.
 """
 import pickle
 
@@ -137,6 +142,58 @@ class PassageEmbeddingStore:
         return D, self.mask[idx].bool() & live.view(-1, 1)
 
 
+class CompressedPassageStore:
+    """The passage store that is nothing but the searcher's resident compressed index: `scorer` is its IndexScorer (the
+    Searcher's `ranker`).  Passage p's embeddings are the rows the reference's CPU branch decompresses and normalises
+    (index_storage.py:160-173), formed inside the kernels from codes, residuals and centroids in fp32 -- whatever numerics mode
+    the scorer searches in.  Every passage has its own length (no Ld, no mask) and nothing is resident beyond the index."""
+
+    def __init__(self, scorer, passage_index2id=None):
+        self.scorer, self.passage_index2id = scorer, passage_index2id
+
+    def __len__(self):
+        return int(self.scorer.arrays.num_passages)
+
+    @property
+    def device(self):
+        return torch.device(scoring._device)
+
+    @property
+    def nbytes(self):
+        return 0   # nothing beyond the index
+
+    def _checked(self, pids):
+        pids = torch.as_tensor(pids).to(self.device)
+        end = int(getattr(self.scorer.arrays, "pid_base", 0)) + len(self)
+        if pids.numel() and int(pids.max()) >= end:   # one device reduction; < 0 is an empty slot
+            raise IndexError(f"pid {int(pids.max())} is outside the index's {len(self)} passages")
+        return pids
+
+    def score(self, Q, pids, config=None):
+        """Q [n, Nq, 128] (fp32 / fp16 / bf16, widened exactly), pids [n, k] as the scorer's search returns them (< 0 = empty
+        slot; a passage of length 0 also scores as an all-padded document) -> f32 [n, k], differentiable in Q; dQ comes back in
+        Q's dtype.  'flipr' reduces the differentiable column maxima with scoring.reduce_colmax.  Raises IndexError for a pid
+        >= len(self) before anything is launched (one device reduction the host waits for, as PassageEmbeddingStore.score)."""
+        pids = self._checked(pids)
+        return scoring.maxsim_index_differentiable(Q.to(self.device), self.scorer.device_index, pids, config)
+
+    def lookup(self, pids, dtype=torch.float32):
+        """The padded copy, for callers that do want it (through scorer.lookup_pids): pids [...] -> (D [pids.numel(), L, 128]
+        in `dtype`, mask bool [pids.numel(), L]) with L the longest of the passages asked for; an empty slot (pid < 0) is a zero
+        document with an all-zero mask."""
+        flat = self._checked(pids).reshape(-1).long()
+        local = flat - int(getattr(self.scorer.arrays, "pid_base", 0))
+        live = (flat >= 0).cpu()
+        packed, lens = self.scorer.lookup_pids(local[live.to(local.device)].cpu(), out_device=self.device)
+        lens_all = torch.zeros(flat.numel(), dtype=torch.int64)
+        lens_all[live] = lens.cpu().long()
+        L = max(int(lens_all.max()) if flat.numel() else 0, 1)
+        mask = (torch.arange(L).unsqueeze(0) < lens_all.unsqueeze(1)).to(self.device)
+        D = torch.zeros((flat.numel(), L, packed.size(-1)), dtype=dtype, device=self.device)
+        D[mask] = packed.to(dtype)
+        return D, mask
+
+
 class RescoreResult:
     """What `retrieve_and_rescore` returns: pids i32 [B, n_docs] (-1 = empty slot), doc_scores f32 [B, n_docs] with a gradient
     to Q, the index's own scores [B, n_docs] (no gradient) and counts i32 [B] = the filled slots of each row, all on the
@@ -157,7 +214,8 @@ class RescoreResult:
 
 def retrieve_and_rescore(searcher, store, Q, n_docs, n_docs_retrieve=None, generator=None, config=None):
     """One training step's retrieval (rag_model_blip.py:392-443): search the index with Q.detach() on the device, then re-score
-    the retrieved passages from `store` under autograd.  Q [B, Nq, 128] (with grad) -> RescoreResult.  `config` is the scoring
+    the retrieved passages from `store` (a PassageEmbeddingStore, or a CompressedPassageStore over the searcher's own index:
+    anything with `device`, `score` and `passage_index2id`) under autograd.  Q [B, Nq, 128] (with grad) -> RescoreResult.  `config` is the scoring
     model's ColBERT config (its `interaction`; None = 'colbert'), as for scoring.colbert_score_differentiable.
 
     The search is the batched branch of `Searcher._search_all_Q` (the searcher's k-policy, sticky on its config;

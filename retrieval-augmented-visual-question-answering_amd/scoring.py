@@ -10,7 +10,8 @@ colbert.py:82-113) -- goes through `colbert_score_differentiable`, `colbert_scor
 gradients from it (flmr_colbert_maxsim_fwd / _bwd), so the [B, Ld, Nq] score tensor is never materialised.  Where the
 documents are passages of a device-resident store picked by pid -- the RAG model's re-scoring of what it has just retrieved --
 `maxsim_gather_differentiable` (rag.PassageEmbeddingStore.score) does the same without building the padded document copy or the
-duplicated queries (flmr_maxsim_gather_fwd / _bwd).
+duplicated queries (flmr_maxsim_gather_fwd / _bwd); `maxsim_index_differentiable` (rag.CompressedPassageStore.score) reads the
+passages' tokens out of the compressed index itself (flmr_maxsim_index_fwd / _bwd), for corpora with no resident store.
 """
 import torch
 
@@ -137,6 +138,44 @@ def maxsim_gather_differentiable(Q, store, store_mask, pids, config=None):
         colmax = _MaxSimGather.apply(Q, store, store_mask, pids, True)
         return reduce_colmax(colmax.flatten(0, 1), config).reshape(pids.shape)
     return _MaxSimGather.apply(Q, store, store_mask, pids, False)
+
+
+class _MaxSimIndex(torch.autograd.Function):
+    """_MaxSimGather whose passage store is the resident compressed index (index.DeviceIndex): the tokens of passage pids[q, j]
+    are decompressed and normalised inside the kernels.  Saves (Q, pids, argmax) and the index by reference; the index is a
+    constant, so Q is the only input with a gradient.  Returns [n, k] sums or [n, k, Nq] column maxima."""
+
+    @staticmethod
+    def forward(ctx, Q, device_index, pids, want_colmax):
+        out, colmax, argmax = ops.maxsim_index_fwd(device_index, Q.detach().float(), pids, want_out=not want_colmax,
+                                                   want_colmax=want_colmax)
+        ctx.save_for_backward(Q, pids, argmax)
+        ctx.device_index, ctx.want_colmax = device_index, want_colmax
+        return colmax if want_colmax else out
+
+    @staticmethod
+    def backward(ctx, grad):
+        Q, pids, argmax = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        G = grad.float() if ctx.want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)
+        dQ = ops.maxsim_index_bwd(ctx.device_index, pids, argmax, G.contiguous())
+        return dQ.to(Q.dtype), None, None, None
+
+
+def maxsim_index_differentiable(Q, device_index, pids, config=None):
+    """maxsim_gather_differentiable from the compressed index: Q [n, Nq, 128] (fp32 / fp16 / bf16, widened exactly), a resident
+    index.DeviceIndex, pids i32 [n, k] as the index's search returns them -> f32 [n, k], differentiable in Q only (dQ in Q's
+    dtype).  Values are colbert_score (-9999 padding, no zero clamp) of Q[q] against the decompressed, normalised tokens of
+    passage pids[q, j] (index_storage.py:160-173) in fp32, whatever numerics mode the searcher runs; a pid < 0 or outside the
+    index and a passage of length 0 score as all-padded documents."""
+    if Q.dim() != 3 or pids.dim() != 2 or pids.size(0) != Q.size(0):
+        raise ValueError(f"Q {tuple(Q.shape)} / pids {tuple(pids.shape)}: expected [n, Nq, d] and [n, k]")
+    Q, pids = Q.to(_device), pids.to(device=_device, dtype=torch.int32)
+    if _interaction(config) == "flipr":
+        colmax = _MaxSimIndex.apply(Q, device_index, pids, True)
+        return reduce_colmax(colmax.flatten(0, 1), config).reshape(pids.shape)
+    return _MaxSimIndex.apply(Q, device_index, pids, False)
 
 
 def colbert_score_differentiable(Q, D_padded, D_mask, config=None):

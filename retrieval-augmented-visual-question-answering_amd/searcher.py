@@ -227,8 +227,13 @@ class Searcher:
     def retrieve_and_rescore(self, Q, store, n_docs, n_docs_retrieve=None, generator=None, config=None):
         """A RAG training step's retrieval on the device (rag_model_blip.py:392-443): search with Q.detach(), then re-score the
         retrieved passages from `store` (rag.PassageEmbeddingStore) under autograd -> rag.RescoreResult (pids, doc_scores with a
-        gradient to Q, index_scores, counts, passage_ids).  See rag.retrieve_and_rescore."""
+        gradient to Q, index_scores, counts, passage_ids).  store=None re-scores from the compressed index this searcher holds: a
+        rag.CompressedPassageStore over `self.ranker`, built on first use and kept.  See rag.retrieve_and_rescore."""
         from . import rag
+        if store is None:
+            store = getattr(self, "_index_store", None)
+            if store is None or store.scorer is not self.ranker:
+                store = self._index_store = rag.CompressedPassageStore(self.ranker)
         return rag.retrieve_and_rescore(self, store, Q, n_docs, n_docs_retrieve=n_docs_retrieve, generator=generator, config=config)
 
     def dense_search(self, Q, k=10, filter_fn=None, remove_zero_tensors=False):
