@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FLMR_ABI_VERSION 9
+#define FLMR_ABI_VERSION 10
 
 typedef enum flmr_status {
     FLMR_OK = 0,
@@ -361,6 +361,45 @@ int flmr_colbert_maxsim_bwd(const float* Q, int32_t q_batch, int32_t nq, const f
                             int32_t cross, const int32_t* argmax, const float* grad_colmax, float* dQ, float* dD,
                             flmr_stream_t stream);
 
+/* The padded MaxSim on HALF-PRECISION operands (what every drop-in caller of the scoring head holds: ColBERT.doc() halves the
+ * documents, TPC/modeling/colbert.py:206, and colbert_score rounds the query to their dtype, :280-284).  The typed entry points
+ * take Q and D as `const void*` with an element type each, FLMR_F32 (0) or FLMR_F16 (1, IEEE half bit patterns); shapes, the
+ * `cross` switch, -9999 padding, tie rule and argmax = -1 are those of flmr_colbert_maxsim_fwd / _bwd above.
+ *
+ * Supported (q_dtype, d_dtype):
+ *   (F32, F32)  forwards to the fp32 entry points above, with their behaviour (flmr_colbert_score_typed inherits the workspace
+ *               and the stream synchronise of flmr_colbert_score_padded / _cross / _colmax_padded);
+ *   (F32, F16)  D rows are used as they are; the low part of their fp16 split is zero, so lo(D) x hi(Q) is not issued: two MFMAs
+ *               per 16 dims instead of three; fp32 Q is split while it is staged (no workspace);
+ *   (F16, F16)  ONE MFMA per 16 dims: neither operand has a low part; Q is staged as it is;
+ *   (F16, F32)  FLMR_ERR_UNSUPPORTED: no caller produces it; widen Q (exact, small) and call the fp32 entry points.
+ * Products of fp16 values are exact in fp32 and the accumulation order is that of the fp32 kernels, so out / colmax / argmax are
+ * BIT-IDENTICAL to the fp32 entry points run on the widened operands.  The half forms use no workspace and do not synchronise.
+ *
+ * flmr_colbert_score_typed: the forward-only scorer.  out f32 [B] (or [q_batch, B] when `cross`) and / or colmax f32 [rows, nq];
+ *   at least one of them non-NULL.
+ * flmr_colbert_maxsim_fwd_typed: the autograd forward: out, colmax (each nullable) and argmax i32 [rows, nq].
+ * flmr_colbert_maxsim_bwd_typed: dQ [q_batch, nq, dim] in dq_dtype and dD [B, Ld, dim] in dd_dtype (each FLMR_F32 or FLMR_F16,
+ *   either pointer nullable).  The sums are formed in fp32 in the fixed orders of flmr_colbert_maxsim_bwd and written once; an
+ *   FLMR_F16 output is that fp32 sum rounded to nearest-even, i.e. the bits of the fp32 gradient of the widened operands
+ *   converted to half.  Deterministic.
+ *
+ * Errors: an unknown dtype, a NULL pointer, a bad q_batch, negative sizes, or Q / D (and dQ / dD) not 16-byte aligned ->
+ * FLMR_ERR_INVALID (all checked on the host before anything is launched); dim != 128, nq * 8 > 64 KiB or the (F16, F32) pair ->
+ * FLMR_ERR_UNSUPPORTED; B == 0 -> FLMR_OK and nothing is launched. */
+#define FLMR_F32 0
+#define FLMR_F16 1
+int flmr_colbert_score_typed(const void* Q, int32_t q_dtype, int32_t q_batch, int32_t nq, const void* D, int32_t d_dtype,
+                             const uint8_t* mask, int32_t B, int32_t Ld, int32_t dim, int32_t cross, float* out, float* colmax,
+                             flmr_stream_t stream);
+int flmr_colbert_maxsim_fwd_typed(const void* Q, int32_t q_dtype, int32_t q_batch, int32_t nq, const void* D, int32_t d_dtype,
+                                  const uint8_t* mask, int32_t B, int32_t Ld, int32_t dim, int32_t cross, float* out,
+                                  float* colmax, int32_t* argmax, flmr_stream_t stream);
+int flmr_colbert_maxsim_bwd_typed(const void* Q, int32_t q_dtype, int32_t q_batch, int32_t nq, const void* D, int32_t d_dtype,
+                                  int32_t B, int32_t Ld, int32_t dim, int32_t cross, const int32_t* argmax,
+                                  const float* grad_colmax, void* dQ, int32_t dq_dtype, void* dD, int32_t dd_dtype,
+                                  flmr_stream_t stream);
+
 /* Retrieve-and-rescore (the re-scoring of retrieved passages under autograd inside the RAG model's training step,
  * src/models/rag/rag_model_blip.py:409-442): the GATHERED forms of flmr_colbert_maxsim_fwd / _bwd.  The documents are not an
  * argument but rows of a device-resident passage store [npassages, Ld, dim] -- fp32 (FLMR_F32) or IEEE half bit patterns
@@ -382,8 +421,6 @@ int flmr_colbert_maxsim_bwd(const float* Q, int32_t q_batch, int32_t nq, const f
  * Both enqueue on `stream`, use no workspace and do not synchronise.  dim != 128 -> FLMR_ERR_UNSUPPORTED; nq * 8 > 64 KiB ->
  * FLMR_ERR_UNSUPPORTED; NULL pointers, negative sizes, an unknown store_dtype, a misaligned Q / store -> FLMR_ERR_INVALID;
  * nqueries * k == 0 -> FLMR_OK and nothing is launched (dQ is then the caller's to zero). */
-#define FLMR_F32 0
-#define FLMR_F16 1
 int flmr_maxsim_gather_fwd(const float* Q, int32_t nqueries, int32_t nq, const void* store, int32_t store_dtype,
                            const uint8_t* store_mask, int32_t npassages, int32_t Ld, int32_t dim, const int32_t* pids, int32_t k,
                            float* out, float* colmax, int32_t* argmax, flmr_stream_t stream);

@@ -96,8 +96,11 @@ def make_colbert_score_dispatch(reference_colbert_score, autograd=False):
     Arithmetic: as in the reference Q is first rounded to D_padded's dtype (colbert.py:280: `Q.to(dtype=D_padded.dtype)`);
     the products of those values are then exact and accumulated in fp32, and only the final per-passage score is rounded to
     D_padded's dtype -- for half / bf16 inputs the reference rounds the [B, Ld, Nq] score matrix and the column sums as well,
-    so scores can differ from it in the last fp16 / bf16 digit (fp32 inputs: within 1e-4, tests).  The result lives where the
-    reference would have put it (the inputs' device; cuda when use_gpu)."""
+    so scores can differ from it in the last fp16 / bf16 digit (fp32 inputs: within 1e-4, tests).  fp16 operands -- what the
+    reference's CUDA path hands over, colbert.py:206 -- go to the kernels as they are: one MFMA per 16 dims, no fp32 copy of Q or
+    D, forward and backward (flmr_colbert_score_typed / _maxsim_fwd_typed / _maxsim_bwd_typed), with the bits the fp32 kernels
+    give the widened values; bf16 operands are widened exactly to fp32 first.  The result lives where the reference would have
+    put it (the inputs' device; cuda when use_gpu)."""
     import torch
     state = {"warned": False}
 

@@ -18,6 +18,11 @@ the text tokens, the L2 normalisation, `keep_dims` handling, and the MaxSim scor
 `differentiable=True` opts into the HIP MaxSim under autograd (scoring.colbert_score_differentiable): `score` then carries
 gradients back to Q and D, and `forward` under grad with `use_ib_negatives` returns `(scores, ib_loss)` as colbert.py:75-78
 does, the loss from scoring.in_batch_negative_loss.
+
+Arithmetic: this class keeps the encoders' fp32 states (`use_gpu = False`: no `D.half()`, colbert.py:206-207), so its scores are
+the fp32 kernels'.  A subclass or caller that halves D as the reference's CUDA path does hands `score` fp16 documents: those are
+scored as they are (fp16 D with fp32 or fp16 Q: no fp32 copy, gradients in each input's dtype), with the bits of the fp32 path on
+the widened values; bf16 is widened exactly to fp32.
 """
 import string
 

@@ -29,6 +29,35 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+# ---- operand dtypes of the padded MaxSim ----------------------------------------------------------------------------------
+# (Q dtype, D dtype) pairs the kernels take as they are (flmr_colbert_*_typed).  Every other pair -- bf16, fp64, and fp16 Q with
+# fp32 D, which no caller produces -- is widened exactly to fp32 first, as before.
+MAXSIM_NATIVE_PAIRS = frozenset({(torch.float32, torch.float32), (torch.float32, torch.float16), (torch.float16, torch.float16)})
+
+
+def maxsim_native_pair(q_dtype, d_dtype):
+    """True when the padded MaxSim runs on these operand dtypes without a widened copy."""
+    return (q_dtype, d_dtype) in MAXSIM_NATIVE_PAIRS
+
+
+def _aligned(t):
+    """CUDA, contiguous, dtype kept; copied when the storage offset breaks the 16-byte alignment the kernels' row loads need."""
+    t = torch.as_tensor(t).to("cuda").contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _maxsim_operands(Q, D):
+    """-> (Q, D, typed): the operands as given for a half pair (typed entry points), else both as fp32 (the fp32 entry points)."""
+    Q, D = torch.as_tensor(Q), torch.as_tensor(D)
+    if maxsim_native_pair(Q.dtype, D.dtype) and D.dtype == torch.float16:
+        return _aligned(Q), _aligned(D), True
+    return _d(Q, torch.float32), _d(D, torch.float32), False
+
+
+def _ft(dtype):
+    return _native.FLMR_F16 if dtype == torch.float16 else _native.FLMR_F32
+
+
 def filter_pids(pids, centroid_scores, codes, doclens, offsets, idx, nfiltered_docs, _codes_dev=None, _offsets_dev=None):
     lib = _native.load()
     pd, cs = _d(pids, torch.int32), _d(centroid_scores, torch.float32)
@@ -84,12 +113,19 @@ def segmented_maxsim(scores, lengths):
 
 
 def colbert_score_padded(Q, D_padded, D_mask):
-    """Forward-only padded MaxSim (colbert.py:268-286): Q [1|B, Nq, d], D [B, Ld, d], mask [B, Ld(,1)] -> [B]."""
+    """Forward-only padded MaxSim (colbert.py:268-286): Q [1|B, Nq, d], D [B, Ld, d], mask [B, Ld(,1)] -> f32 [B].  fp16 D with
+    fp16 or fp32 Q is scored as it is (flmr_colbert_score_typed: no fp32 copy, no workspace, no synchronise), with the bits of the
+    fp32 kernel on the widened operands; every other dtype pair is widened exactly to fp32."""
     lib = _native.load()
-    Qd, Dd = _d(Q, torch.float32), _d(D_padded, torch.float32)
+    Qd, Dd, typed = _maxsim_operands(Q, D_padded)
     B, Ld, dim = Dd.shape
     md = _d(torch.as_tensor(D_mask).reshape(B, Ld), torch.bool).view(torch.uint8)
     out = torch.empty(B, dtype=torch.float32, device="cuda")
+    if typed:
+        if B:
+            _native.check(lib.flmr_colbert_score_typed(_p(Qd), _ft(Qd.dtype), Qd.size(0), Qd.size(1), _p(Dd), _ft(Dd.dtype), _p(md), B, Ld,
+                                                       dim, 0, _p(out), None, _native.stream_ptr()))
+        return out
     _native.check(lib.flmr_colbert_score_padded(_p(Qd), Qd.size(0), Qd.size(1), _p(Dd), _p(md), B, Ld, dim, _p(out),
                                                 _native.stream_ptr()))
     return out
@@ -97,12 +133,17 @@ def colbert_score_padded(Q, D_padded, D_mask):
 
 def colbert_score_cross(Q, D_padded, D_mask):
     """Every query against every document in ONE launch: Q [nqueries, Nq, d], D [B, Ld, d], mask [B, Ld(,1)] -> [nqueries, B]
-    (the rate matrix of the executor's exhaustive search, FLMR_executor.py:799-847)."""
+    (the rate matrix of the executor's exhaustive search, FLMR_executor.py:799-847).  Operand dtypes as colbert_score_padded."""
     lib = _native.load()
-    Qd, Dd = _d(Q, torch.float32), _d(D_padded, torch.float32)
+    Qd, Dd, typed = _maxsim_operands(Q, D_padded)
     B, Ld, dim = Dd.shape
     md = _d(torch.as_tensor(D_mask).reshape(B, Ld), torch.bool).view(torch.uint8)
     out = torch.empty((Qd.size(0), B), dtype=torch.float32, device="cuda")
+    if typed:
+        if B and Qd.size(0):
+            _native.check(lib.flmr_colbert_score_typed(_p(Qd), _ft(Qd.dtype), Qd.size(0), Qd.size(1), _p(Dd), _ft(Dd.dtype), _p(md), B, Ld,
+                                                       dim, 1, _p(out), None, _native.stream_ptr()))
+        return out
     _native.check(lib.flmr_colbert_score_cross(_p(Qd), Qd.size(0), Qd.size(1), _p(Dd), _p(md), B, Ld, dim, _p(out),
                                                _native.stream_ptr()))
     return out
@@ -110,25 +151,33 @@ def colbert_score_cross(Q, D_padded, D_mask):
 
 def colbert_colmax_padded(Q, D_padded, D_mask):
     """The per-column maxima [B, Nq] of the padded MaxSim (-9999 padding) before their sum: what `colbert_score_reduce`
-    reduces -- by a plain sum for 'colbert', by top-k sums for 'flipr' (colbert.py:235-263)."""
+    reduces -- by a plain sum for 'colbert', by top-k sums for 'flipr' (colbert.py:235-263).  Operand dtypes as
+    colbert_score_padded."""
     lib = _native.load()
-    Qd, Dd = _d(Q, torch.float32), _d(D_padded, torch.float32)
+    Qd, Dd, typed = _maxsim_operands(Q, D_padded)
     B, Ld, dim = Dd.shape
     md = _d(torch.as_tensor(D_mask).reshape(B, Ld), torch.bool).view(torch.uint8)
     out = torch.empty((B, Qd.size(1)), dtype=torch.float32, device="cuda")
+    if typed:
+        if B:
+            _native.check(lib.flmr_colbert_score_typed(_p(Qd), _ft(Qd.dtype), Qd.size(0), Qd.size(1), _p(Dd), _ft(Dd.dtype), _p(md), B, Ld,
+                                                       dim, 0, None, _p(out), _native.stream_ptr()))
+        return out
     _native.check(lib.flmr_colbert_colmax_padded(_p(Qd), Qd.size(0), Qd.size(1), _p(Dd), _p(md), B, Ld, dim, _p(out),
                                                  _native.stream_ptr()))
     return out
 
 
 def colbert_maxsim_fwd(Q, D_padded, D_mask, cross=False, want_out=True, want_colmax=False):
-    """The autograd forward (flmr_colbert_maxsim_fwd): fp32 CUDA Q [q_batch, Nq, 128], D [B, Ld, 128], mask [B, Ld(,1)] ->
+    """The autograd forward (flmr_colbert_maxsim_fwd / _fwd_typed): CUDA Q [q_batch, Nq, 128], D [B, Ld, 128], mask [B, Ld(,1)] ->
     (out f32 [rows] | None, colmax f32 [rows, Nq] | None, argmax i32 [rows, Nq]); rows = B, or q_batch * B query-major when
     `cross` (returned there as [q_batch, B] / [q_batch, B, Nq]).  argmax = the winning token, lowest on ties, -1 where the
     winner is padded.  out / colmax are bit-identical to colbert_score_padded / colbert_score_cross / colbert_colmax_padded.
-    Enqueued on the current stream, no synchronisation."""
+    Native operand dtypes (MAXSIM_NATIVE_PAIRS): fp32 Q and D; fp16 D with fp32 or fp16 Q, read as they are with the bits of the
+    fp32 kernel on the widened values.  Any other pair is widened exactly to fp32.  Enqueued on the current stream, no
+    synchronisation."""
     lib = _native.load()
-    Qd, Dd = _d(Q, torch.float32), _d(D_padded, torch.float32)
+    Qd, Dd, typed = _maxsim_operands(Q, D_padded)
     B, Ld, dim = Dd.shape
     nQ, nq = Qd.size(0), Qd.size(1)
     md = _d(torch.as_tensor(D_mask).reshape(B, Ld), torch.bool).view(torch.uint8)
@@ -138,30 +187,43 @@ def colbert_maxsim_fwd(Q, D_padded, D_mask, cross=False, want_out=True, want_col
     argmax = torch.empty(lead + (nq,), dtype=torch.int32, device="cuda")
     if B == 0:
         return out, colmax, argmax   # (empty tensors may have NULL data pointers, which the C ABI rejects)
+    if typed:
+        _native.check(lib.flmr_colbert_maxsim_fwd_typed(_p(Qd), _ft(Qd.dtype), nQ, nq, _p(Dd), _ft(Dd.dtype), _p(md), B, Ld, dim,
+                                                        int(bool(cross)), _p(out), _p(colmax), _p(argmax), _native.stream_ptr()))
+        return out, colmax, argmax
     _native.check(lib.flmr_colbert_maxsim_fwd(_p(Qd), nQ, nq, _p(Dd), _p(md), B, Ld, dim, int(bool(cross)), _p(out), _p(colmax),
                                               _p(argmax), _native.stream_ptr()))
     return out, colmax, argmax
 
 
-def colbert_maxsim_bwd(Q, D_padded, argmax, grad_colmax, cross=False, need_dQ=True, need_dD=True):
-    """The autograd backward (flmr_colbert_maxsim_bwd): from the forward's argmax and G = dL/dcolmax (shaped like argmax) ->
-    (dQ f32 [q_batch, Nq, 128] | None, dD f32 [B, Ld, 128] | None).  Deterministic; enqueued on the current stream."""
+def colbert_maxsim_bwd(Q, D_padded, argmax, grad_colmax, cross=False, need_dQ=True, need_dD=True, dq_dtype=torch.float32,
+                       dd_dtype=torch.float32):
+    """The autograd backward (flmr_colbert_maxsim_bwd / _bwd_typed): from the forward's argmax and G = dL/dcolmax (shaped like
+    argmax) -> (dQ [q_batch, Nq, 128] | None in dq_dtype, dD [B, Ld, 128] | None in dd_dtype; fp32 unless asked otherwise).
+    Operand dtypes as colbert_maxsim_fwd.  The sums are fp32 in a fixed order; an fp16 gradient is written by the kernel itself,
+    rounded once (the bits of the fp32 gradient `.to(torch.float16)`); any other gradient dtype is converted from the fp32 result.
+    Deterministic; enqueued on the current stream."""
     lib = _native.load()
-    Qd, Dd = _d(Q, torch.float32), _d(D_padded, torch.float32)
+    Qd, Dd, typed = _maxsim_operands(Q, D_padded)
+    kdt = (torch.float32, torch.float16)
+    oq, od = (dq_dtype if typed and dq_dtype in kdt else torch.float32), (dd_dtype if typed and dd_dtype in kdt else torch.float32)
     B, Ld, dim = Dd.shape
     nQ, nq = Qd.size(0), Qd.size(1)
     am, G = _d(argmax, torch.int32), _d(grad_colmax, torch.float32)
     rows = nQ * B if cross else B
     assert am.numel() == rows * nq and G.numel() == rows * nq, (tuple(am.shape), tuple(G.shape), rows, nq)
-    dQ = torch.empty_like(Qd) if need_dQ else None
-    dD = torch.empty_like(Dd) if need_dD else None
+    dQ = torch.empty(Qd.shape, dtype=oq, device="cuda") if need_dQ else None
+    dD = torch.empty(Dd.shape, dtype=od, device="cuda") if need_dD else None
     if B == 0:
         if dQ is not None:
             dQ.zero_()
-        return dQ, dD
-    _native.check(lib.flmr_colbert_maxsim_bwd(_p(Qd), nQ, nq, _p(Dd), B, Ld, dim, int(bool(cross)), _p(am), _p(G), _p(dQ), _p(dD),
-                                              _native.stream_ptr()))
-    return dQ, dD
+    elif typed:
+        _native.check(lib.flmr_colbert_maxsim_bwd_typed(_p(Qd), _ft(Qd.dtype), nQ, nq, _p(Dd), _ft(Dd.dtype), B, Ld, dim, int(bool(cross)),
+                                                        _p(am), _p(G), _p(dQ), _ft(oq), _p(dD), _ft(od), _native.stream_ptr()))
+    else:
+        _native.check(lib.flmr_colbert_maxsim_bwd(_p(Qd), nQ, nq, _p(Dd), B, Ld, dim, int(bool(cross)), _p(am), _p(G), _p(dQ), _p(dD),
+                                                  _native.stream_ptr()))
+    return (dQ.to(dq_dtype) if dQ is not None else None), (dD.to(dd_dtype) if dD is not None else None)
 
 
 def _store_dtype(store):

@@ -16,6 +16,7 @@ passages' tokens out of the compressed index itself (flmr_maxsim_index_fwd / _bw
 import torch
 
 from . import ops
+from .ops import maxsim_native_pair
 
 
 def _no_grad_only(*tensors):
@@ -66,12 +67,23 @@ _device = "cuda"   # where the kernels run (the CPU plumbing tests point this at
 class _MaxSim(torch.autograd.Function):
     """Padded MaxSim with the gradient torch's autograd gives colbert_score_reduce (colbert.py:235-263): each column's
     gradient goes to its winning token, the lowest one on ties, and nowhere when that token is padded.  Returns the kernel's
-    per-row sum (`colbert`, [rows]) or the per-column maxima ([rows, Nq]); rows are [nQ, B] in the cross form."""
+    per-row sum (`colbert`, [rows]) or the per-column maxima ([rows, Nq]); rows are [nQ, B] in the cross form.
+
+    Operand dtypes: fp32 Q and D, and fp16 D with fp32 or fp16 Q (what a drop-in training step holds), go to the kernels as they
+    are -- no fp32 copy is made, the operands are saved as given and the backward writes each gradient in its input's dtype.
+    Every other pair (bf16, fp64, fp16 Q with fp32 D) is widened exactly to fp32 for the kernels and its gradients are converted
+    back."""
+
+    @staticmethod
+    def _operands(Q, D_padded):
+        if maxsim_native_pair(Q.dtype, D_padded.dtype):
+            return Q.detach(), D_padded.detach(), True
+        return Q.detach().float(), D_padded.detach().float(), False
 
     @staticmethod
     def forward(ctx, Q, D_padded, D_mask, cross, want_colmax):
-        out, colmax, argmax = ops.colbert_maxsim_fwd(Q.detach().float(), D_padded.detach().float(), D_mask, cross=cross,
-                                                     want_out=not want_colmax, want_colmax=want_colmax)
+        Qk, Dk, _ = _MaxSim._operands(Q, D_padded)
+        out, colmax, argmax = ops.colbert_maxsim_fwd(Qk, Dk, D_mask, cross=cross, want_out=not want_colmax, want_colmax=want_colmax)
         ctx.save_for_backward(Q, D_padded, argmax)
         ctx.cross, ctx.want_colmax = cross, want_colmax
         return colmax if want_colmax else out
@@ -83,8 +95,12 @@ class _MaxSim(torch.autograd.Function):
         if not (need_dQ or need_dD):
             return None, None, None, None, None
         G = grad.float() if ctx.want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)
-        dQ, dD = ops.colbert_maxsim_bwd(Q.detach().float(), D_padded.detach().float(), argmax, G.contiguous(), cross=ctx.cross,
-                                        need_dQ=need_dQ, need_dD=need_dD)
+        Qk, Dk, native = _MaxSim._operands(Q, D_padded)
+        if native and (Q.dtype, D_padded.dtype) != (torch.float32, torch.float32):   # the kernels write each input's dtype
+            dQ, dD = ops.colbert_maxsim_bwd(Qk, Dk, argmax, G.contiguous(), cross=ctx.cross, need_dQ=need_dQ, need_dD=need_dD,
+                                            dq_dtype=Q.dtype, dd_dtype=D_padded.dtype)
+            return dQ, dD, None, None, None
+        dQ, dD = ops.colbert_maxsim_bwd(Qk, Dk, argmax, G.contiguous(), cross=ctx.cross, need_dQ=need_dQ, need_dD=need_dD)
         return (dQ.to(Q.dtype) if need_dQ else None, dD.to(D_padded.dtype) if need_dD else None, None, None, None)
 
 
@@ -180,8 +196,9 @@ def maxsim_index_differentiable(Q, device_index, pids, config=None):
 
 def colbert_score_differentiable(Q, D_padded, D_mask, config=None):
     """colbert_score (colbert.py:268-286) under autograd: Q [1|B, Nq, 128], D [B, Ld, 128] -> f32 [B] on the device, with
-    dQ / dD equal to what torch's autograd gives the reference expression.  fp16 / bf16 inputs are widened exactly to fp32;
-    gradients come back in each input's dtype.  'colbert' values are bit-identical to ops.colbert_score_padded; 'flipr'
+    dQ / dD equal to what torch's autograd gives the reference expression.  fp16 D with fp16 or fp32 Q runs natively (no fp32
+    copy; the bits of the fp32 path on the widened values); bf16 and every other pair are widened exactly to fp32.  Gradients
+    come back in each input's dtype.  'colbert' values are bit-identical to ops.colbert_score_padded; 'flipr'
     reduces the differentiable column maxima with reduce_colmax."""
     return _maxsim(Q, D_padded, D_mask, config, cross=False)
 
@@ -241,17 +258,22 @@ def exhaustive_search(query_embeddings, item_embeddings, item_embedding_mask, k,
     query_embeddings [nq, Nq, d]; item_embeddings [n_items, Ld, d]; item_embedding_mask [n_items, Ld(,1)] (1 = real token).
     Returns (indices int64 [nq, k'], scores f32 [nq, k'], rate_batch f32 [nq, n_items]) on the device, k' = min(k, n_items).
     One launch of the padded MaxSim kernel per item chunk scores EVERY query against the chunk's items (the cross form,
-    `flmr_colbert_score_cross`); `item_chunk` bounds the items resident per launch for corpora larger than HBM headroom."""
+    `flmr_colbert_score_cross`); `item_chunk` bounds the items resident per launch for corpora larger than HBM headroom.
+    fp16 items (with fp16 or fp32 queries) are moved and scored chunk by chunk as fp16, with the bits of the run on their fp32
+    image; other dtypes are widened to fp32 per chunk."""
     _no_grad_only(query_embeddings, item_embeddings)
-    Q = torch.as_tensor(query_embeddings).to("cuda", torch.float32)
+    Q = torch.as_tensor(query_embeddings).to("cuda")
     D = torch.as_tensor(item_embeddings)
+    native = maxsim_native_pair(Q.dtype, D.dtype)
+    if not native:
+        Q = Q.float()
     M = torch.as_tensor(item_embedding_mask)
     n_items = D.size(0)
     M = M.reshape(n_items, -1)
     item_chunk = item_chunk or n_items
     rate = torch.empty((Q.size(0), n_items), dtype=torch.float32, device="cuda")
     for i0 in range(0, n_items, item_chunk):
-        Dc = D[i0:i0 + item_chunk].to("cuda", torch.float32).contiguous()
+        Dc = D[i0:i0 + item_chunk].to("cuda", D.dtype if native else torch.float32).contiguous()
         Mc = M[i0:i0 + item_chunk].to("cuda")
         for q0 in range(0, Q.size(0), 65535):   # (grid dimension limit of the cross form)
             rate[q0:q0 + 65535, i0:i0 + Dc.size(0)] = ops.colbert_score_cross(Q[q0:q0 + 65535], Dc, Mc)
