@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FLMR_ABI_VERSION 10
+#define FLMR_ABI_VERSION 11
 
 typedef enum flmr_status {
     FLMR_OK = 0,
@@ -450,6 +450,34 @@ int flmr_maxsim_index_fwd(const flmr_index_t* index, const float* Q, int32_t nqu
                           float* out, float* colmax, int32_t* argmax, flmr_stream_t stream);
 int flmr_maxsim_index_bwd(const flmr_index_t* index, const int32_t* pids, int32_t nqueries, int32_t k, int32_t nq,
                           const int32_t* argmax, const float* grad_colmax, float* dQ, flmr_stream_t stream);
+
+/* The RAG-sequence marginalised loss's token log-likelihoods (RagModelForBlip.get_loss, src/models/rag/rag_model_blip.py:826-1026:
+ * log_softmax(seq_logits).gather(-1, target) and its backward) as one streaming pass each over the logits, so that neither the
+ * [R, T, V] log-probabilities nor their gradient image is built.  logits [R, T, V] in `dtype` -- FLMR_F32, FLMR_F16 (IEEE half
+ * bit patterns) or FLMR_BF16 (bfloat16 bit patterns), widened exactly, all arithmetic in fp32 -- with unit stride along V and
+ * ELEMENT strides stride_r, stride_t >= 0 (a [:, :-1, :] view and a [..., :V] view of a wider buffer are read in place); rows
+ * need not be 16-byte aligned (odd V with a 2-byte type).  target i64 [R, T] contiguous; a position whose target is
+ * ignore_index -- or outside [0, V): the caller's error, callers validate; the kernels never index with it -- is IGNORED.
+ * flmr_rag_token_ll_fwd: for every live (r, t): lse f32 [R, T, 2] (8-byte aligned) = the log-sum-exp of the row in two words,
+ *   lse[r, t] = (m, l) with m = max_v x[v] and l = log sum_v exp(x[v] - m) (online maximum and sum, the running maximum starting at
+ *   -inf, so -inf logits contribute nothing), and ll f32 [R, T] = (x[target] - m) - l.  The words stay apart because the backward's
+ *   exp((x - m) - l) keeps probabilities near 1 to ~6e-8, which exp(x - (m + l)) with the sum rounded to one fp32 does not.  An
+ *   ignored position is not read and gets ll = 0, lse = (0, 0).  Row (r, 0) is read whether ignored or not: first_argmax i32 [R]
+ *   (nullable) = the lowest index of its maximum.
+ * flmr_rag_token_ll_bwd: dlogits [R, T, V] CONTIGUOUS in `dtype` (the fp32 value rounded once to nearest-even),
+ *     dlogits[r, t, v] = grad_ll[r, t] * ([v == target] - exp((x[v] - m) - l));
+ *   every element is written: ignored positions are zeros and their logits are not read.
+ * One workgroup per token row, per-lane (max, sum) pairs merged across lanes and waves in a fixed order, no atomics: two calls give
+ * the same bits.  Both enqueue on `stream`, use no workspace and do not synchronise.  An unknown dtype or a negative stride ->
+ * FLMR_ERR_UNSUPPORTED; NULL pointers, R or T < 0, V < 1, a pointer not aligned to its element -> FLMR_ERR_INVALID; R * T == 0 ->
+ * FLMR_OK and nothing is launched. */
+#define FLMR_BF16 2
+int flmr_rag_token_ll_fwd(const void* logits, int32_t dtype, int64_t R, int64_t T, int64_t V, int64_t stride_r, int64_t stride_t,
+                          const int64_t* target, int64_t ignore_index, float* ll, float* lse, int32_t* first_argmax,
+                          flmr_stream_t stream);
+int flmr_rag_token_ll_bwd(const void* logits, int32_t dtype, int64_t R, int64_t T, int64_t V, int64_t stride_r, int64_t stride_t,
+                          const int64_t* target, int64_t ignore_index, const float* lse, const float* grad_ll, void* dlogits,
+                          flmr_stream_t stream);
 
 /* Merge per-shard top-k lists after the RCCL all-gather: scores f32[nshards, nqueries, k],
  * pids i32[nshards, nqueries, k] (-1 = empty) -> global top-k per query in descending (score,pid) order. */

@@ -14,7 +14,8 @@ from .index import DeviceIndex, IndexArrays, codec_tables, load_index_arrays
 __all__ = ["ColBERTConfig", "RunConfig", "Run", "Queries", "Ranking", "Collection", "Provenance", "IndexArrays",
            "DeviceIndex", "load_index_arrays", "codec_tables", "build_native", "FlmrNativeError", "Searcher",
            "IndexScorer", "install", "uninstall", "installed", "Indexer", "FLMRModelForRetrieval", "ChunkedIndexBuilder",
-           "chunks_of_rank", "PassageEmbeddingStore", "CompressedPassageStore", "retrieve_and_rescore"]
+           "chunks_of_rank", "PassageEmbeddingStore", "CompressedPassageStore", "retrieve_and_rescore",
+           "marginalised_loss", "token_log_likelihood"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported lazily
@@ -30,7 +31,7 @@ def __getattr__(name):  # torch-dependent pieces are imported lazily
     if name in ("ChunkedIndexBuilder", "chunks_of_rank"):
         from . import indexing
         return getattr(indexing, name)
-    if name in ("PassageEmbeddingStore", "CompressedPassageStore", "retrieve_and_rescore"):
+    if name in ("PassageEmbeddingStore", "CompressedPassageStore", "retrieve_and_rescore", "marginalised_loss", "token_log_likelihood"):
         from . import rag
         return getattr(rag, name)
     if name == "FLMRModelForRetrieval":

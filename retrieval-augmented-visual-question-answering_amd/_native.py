@@ -12,15 +12,16 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(PKG_DIR)
 LIB_PATH = os.environ.get("FLMR_HIP_LIB") or os.path.join(PKG_DIR, "lib", "libflmr_hip.so")  # override: A/B-ing kernel builds
 CSRC = os.path.join(PKG_DIR, "csrc")
-SOURCES = ["flmr_index.hip", "flmr_stage0.hip", "flmr_candidates.hip", "flmr_filter.hip", "flmr_stage1_dense.hip", "flmr_stage2_walk.hip", "flmr_stage2_xcd.hip", "flmr_maxsim.hip", "flmr_search.hip", "flmr_ops.hip", "flmr_build.hip", "flmr_build_f16.hip", "flmr_ivf.hip", "flmr_collective.hip", "flmr_score_grad.hip", "flmr_rescore.hip", "flmr_score_half.hip"]
+SOURCES = ["flmr_index.hip", "flmr_stage0.hip", "flmr_candidates.hip", "flmr_filter.hip", "flmr_stage1_dense.hip", "flmr_stage2_walk.hip", "flmr_stage2_xcd.hip", "flmr_maxsim.hip", "flmr_search.hip", "flmr_ops.hip", "flmr_build.hip", "flmr_build_f16.hip", "flmr_ivf.hip", "flmr_collective.hip", "flmr_score_grad.hip", "flmr_rescore.hip", "flmr_score_half.hip", "flmr_rag_loss.hip"]
 HEADERS = ["flmr_common.h", "flmr_device.h"]
 
 FLMR_MEM_HOST, FLMR_MEM_DEVICE = 0, 1
+FLMR_BF16 = 2              # (with the two below) the logits dtype of flmr_rag_token_ll_fwd / _bwd
 FLMR_F32, FLMR_F16 = 0, 1   # store_dtype of flmr_maxsim_gather_fwd / _bwd; q_dtype / d_dtype / dq_dtype / dd_dtype of the typed MaxSim
 (TAP_CENTROID_SCORES, TAP_IDX_BITS, TAP_CELLS, TAP_CANDIDATES, TAP_STAGE1, TAP_STAGE2, TAP_DOC_SCORES, TAP_Q_ERR,
  TAP_Q_ERR_SUM, TAP_STAGE1_FORM) = range(10)
 NUM_STAGES = 9
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class FlmrNativeError(RuntimeError):
@@ -187,6 +188,10 @@ _SIGS = {
                                         C.c_void_p, C.c_void_p]),
     "flmr_maxsim_index_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "flmr_rag_token_ll_fwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flmr_rag_token_ll_bwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flmr_topk_allgather": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flmr_keys_allgather": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -7,6 +7,8 @@
     segmented_lookup(input, pids, lengths, offsets)                                segmented_lookup.cpp:127-144
     segmented_maxsim(scores, lengths)                                              segmented_maxsim.cpp:49-93
 
+and of the training-side pairs (padded / gathered / index MaxSim forward and backward, the RAG loss's token log-likelihoods).
+
 Inputs may be CPU tensors (as the reference passes them): they are staged to HBM, the HIP kernel runs, and the
 result comes back as a CPU tensor like the reference's.  CUDA inputs are used in place.  There is no CPU
 implementation behind these functions.
@@ -315,6 +317,83 @@ def maxsim_index_bwd(device_index, pids, argmax, grad_colmax):
     dQ = torch.empty((n, nq, dim), dtype=torch.float32, device="cuda")
     _native.check(lib.flmr_maxsim_index_bwd(device_index.handle, _p(pd), n, k, nq, _p(am), _p(G), _p(dQ), _native.stream_ptr()))
     return dQ
+
+
+# ---- token log-likelihoods of the RAG marginalised loss ---------------------------------------------------------------------
+_RAG_DTYPES = {torch.float32: _native.FLMR_F32, torch.float16: _native.FLMR_F16, torch.bfloat16: _native.FLMR_BF16}
+
+
+def checked_rag_targets(target, R, T, V, ignore_index, device):
+    """target [R, T] (any integer dtype) -> contiguous int64 on `device`, used in place when it already is that.  A value that is
+    neither ignore_index nor in [0, V) raises IndexError before anything is launched: one device reduction whose result the host
+    waits for (as rag.PassageEmbeddingStore._checked), so a call synchronises with the device once."""
+    tgt = torch.as_tensor(target)
+    if tuple(tgt.shape) != (R, T) or tgt.is_floating_point() or tgt.dtype == torch.bool:
+        raise ValueError(f"target {tuple(tgt.shape)} {tgt.dtype}: expected integers [{R}, {T}]")
+    tgt = tgt.to(device=device, dtype=torch.int64).contiguous()
+    bad = ((tgt < 0) | (tgt >= V)) & (tgt != ignore_index)
+    if tgt.numel() and bool(bad.any()):
+        raise IndexError(f"target {int(tgt[bad][0])} is neither ignore_index ({ignore_index}) nor in [0, {V})")
+    return tgt
+
+
+def _rag_logits(logits):
+    """CUDA [R, T, V] fp32 / fp16 / bf16, read in place through its r and t strides; copied only when the last stride is not 1."""
+    x = torch.as_tensor(logits)
+    if x.dim() != 3 or x.dtype not in _RAG_DTYPES:
+        raise TypeError(f"logits {tuple(x.shape)} {x.dtype}: expected [R, T, V] in fp32, fp16 or bf16")
+    if x.size(2) < 1:
+        raise ValueError("logits with an empty vocabulary")
+    x = x.to("cuda")
+    if (x.size(2) > 1 and x.stride(2) != 1) or min(x.stride(0), x.stride(1)) < 0:
+        x = x.contiguous()
+    return x
+
+
+def rag_token_ll_fwd(logits, target, ignore_index=-100, validate=True):
+    """flmr_rag_token_ll_fwd: logits [R, T, V] (fp32 / fp16 / bf16, any r and t strides: a [:, :-1, :] view and a [..., :V] view
+    of a wider buffer are read where they are), target [R, T] -> (ll f32 [R, T], lse f32 [R, T, 2], first_argmax i32 [R]).
+    ll = logits[target] - logsumexp(logits) per position, in fp32 from one pass over the row; lse holds the log-sum-exp as its two
+    words (row maximum, log of the sum of exp(x - maximum)): lse.sum(-1) is the value, the pair is what the backward needs to keep
+    probabilities near 1 exact to fp32 roundoff.  Positions whose target is ignore_index are not read and hold ll = 0, lse = (0, 0); first_argmax[r] is the lowest index of the maximum of row (r, 0), ignored or
+    not.  Other targets outside [0, V) raise IndexError (checked_rag_targets: the one point where the host waits for the device;
+    validate=False skips it for a target already checked -- the kernels treat such a value as ignored, they never index with it).
+    Enqueued on the current stream."""
+    lib = _native.load()
+    x = _rag_logits(logits)
+    R, T, V = x.shape
+    tgt = checked_rag_targets(target, R, T, V, ignore_index, "cuda") if validate else _d(target, torch.int64)
+    ll = torch.empty((R, T), dtype=torch.float32, device="cuda")
+    lse = torch.empty((R, T, 2), dtype=torch.float32, device="cuda")
+    first = torch.zeros((R,), dtype=torch.int32, device="cuda")
+    if R * T == 0:
+        return ll, lse, first   # (empty tensors may have NULL data pointers, which the C ABI rejects)
+    _native.check(lib.flmr_rag_token_ll_fwd(_p(x), _RAG_DTYPES[x.dtype], R, T, V, x.stride(0), x.stride(1), _p(tgt), int(ignore_index),
+                                            _p(ll), _p(lse), _p(first), _native.stream_ptr()))
+    return ll, lse, first
+
+
+def rag_token_ll_bwd(logits, target, lse, grad_ll, ignore_index=-100, out=None):
+    """flmr_rag_token_ll_bwd: the forward's logits, target (as the forward validated it) and lse [R, T, 2], and grad_ll = dL/dll [R, T] ->
+    dlogits [R, T, V] contiguous in the logits' dtype = grad_ll * (onehot(target) - exp((logits - lse[..., 0]) - lse[..., 1])), the fp32 value rounded
+    once.  Every element is written (`out`, if given, may hold anything): ignored positions are zeros and are not read.
+    Deterministic; enqueued on the current stream."""
+    lib = _native.load()
+    x = _rag_logits(logits)
+    R, T, V = x.shape
+    tgt = _d(target, torch.int64)
+    lse_d, g = _d(lse, torch.float32), _d(grad_ll, torch.float32)
+    assert tuple(tgt.shape) == (R, T) and tuple(lse_d.shape) == (R, T, 2) and tuple(g.shape) == (R, T), (tuple(x.shape), tuple(tgt.shape),
+                                                                                                   tuple(lse_d.shape), tuple(g.shape))
+    if out is None:
+        out = torch.empty((R, T, V), dtype=x.dtype, device="cuda")
+    elif not (out.is_cuda and out.dtype == x.dtype and tuple(out.shape) == (R, T, V) and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous CUDA {x.dtype} tensor {(R, T, V)}")
+    if R * T == 0:
+        return out
+    _native.check(lib.flmr_rag_token_ll_bwd(_p(x), _RAG_DTYPES[x.dtype], R, T, V, x.stride(0), x.stride(1), _p(tgt), int(ignore_index),
+                                            _p(lse_d), _p(g), _p(out), _native.stream_ptr()))
+    return out
 
 
 def merge_topk(scores, pids):

@@ -17,15 +17,24 @@ fp16 = 14.4 GB).  A corpus too large for that -- the 1 M and 6 M passage corpora
 compressed index the searcher already holds: `CompressedPassageStore` (what `retrieve_and_rescore(Q, None, n_docs)` builds)
 scores through flmr_maxsim_index_fwd / _bwd, which decode the passages' tokens inside the kernels, so there is no pickle, no
 second copy of the corpus and no common padded length.  Out of scope there: a gradient to the documents, the
-gpu-fp16 numerics mode (the re-score is always the fp32 CPU-path definition), ShardedSearcher, dim != 128, the prediction-file
-reader and the marginalised loss.
+gpu-fp16 numerics mode (the re-score is always the fp32 CPU-path definition), ShardedSearcher, dim != 128 and the
+prediction-file reader.
+
+The step ends in `RagModelForBlip.get_loss` (:826-1026), where doc_scores meets the generator's logits [B * n_docs, T, V] in the
+RAG-sequence marginalisation.  `marginalised_loss` is that call: the one part that touches the logits -- log_softmax and the gather
+at the targets -- is `token_log_likelihood`, a fused HIP pair (flmr_rag_token_ll_fwd / _bwd) that reads the logits once per
+direction, skips ignored positions and keeps 12 bytes per position; everything after it is torch on [B, n_docs, T] or smaller.
+
+    out = rag.marginalised_loss(logits, r.doc_scores, generator_labels, n_docs, bos_token_id=generator.config.bos_token_id,
+                                retrieval_labels=retrieval_labels, loss_type=config.model_config.RAVQA_loss_type)   # replaces :708-715
+    loss = sum(out[name] * ratio for name, ratio in loss_ratio.items() if ratio != 0)
 """
 import pickle
 
 import numpy as np
 import torch
 
-from . import scoring
+from . import ops, scoring
 
 
 def _rows(x, i0, i1):
@@ -254,3 +263,126 @@ def retrieve_and_rescore(searcher, store, Q, n_docs, n_docs_retrieve=None, gener
     counts = (pids >= 0).sum(dim=1).to(torch.int32)
     doc_scores = store.score(Q, pids.contiguous(), config)
     return RescoreResult(pids, doc_scores, scores, counts, store)
+
+
+# ---- the marginalised loss (rag_model_blip.py:826-1026) -----------------------------------------------------------------------
+LOSS_TYPES = ("Approach1", "Approach2", "Approach3", "Approach4", "Approach5", "Approach6", "NoPR")
+LOSS_NAMES = ("nll_loss", "rag_loss", "additional_loss")
+
+
+class _TokenLL(torch.autograd.Function):
+    """log_softmax(logits).gather(-1, target), masked, without the log-probabilities: saves the logits the caller already holds,
+    the target and lse f32 [R, T, 2]; the backward writes dlogits once, in the logits' dtype."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index):
+        ll, lse, first_argmax = ops.rag_token_ll_fwd(logits.detach(), target, ignore_index)
+        ctx.save_for_backward(logits, target, lse)
+        ctx.ignore_index = ignore_index
+        ctx.mark_non_differentiable(first_argmax)
+        return ll, first_argmax
+
+    @staticmethod
+    def backward(ctx, grad_ll, _):
+        logits, target, lse = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        dlogits = ops.rag_token_ll_bwd(logits.detach(), target, lse, grad_ll.float().contiguous(), ctx.ignore_index)
+        return dlogits, None, None
+
+
+def token_log_likelihood(seq_logits, target, ignore_index=-100):
+    """seq_logits [R, T, V] (fp32 / fp16 / bf16; any strides with a unit last one are read in place), target integers [R, T] ->
+    (ll f32 [R, T], first_argmax i32 [R]).  ll[r, t] = log_softmax(seq_logits[r, t])[target[r, t]] in fp32, 0 where the target is
+    ignore_index (those positions are never read), differentiable with respect to the logits (the gradient comes back in their
+    dtype); first_argmax[r] = the lowest index of the maximum of seq_logits[r, 0].  A target that is neither ignore_index nor in
+    [0, V) raises IndexError before anything is launched (one device reduction the host waits for); `target` is not modified."""
+    if seq_logits.dim() != 3 or tuple(target.shape) != tuple(seq_logits.shape[:2]):
+        raise ValueError(f"seq_logits {tuple(seq_logits.shape)} / target {tuple(target.shape)}: expected [R, T, V] and [R, T]")
+    return _TokenLL.apply(seq_logits, target, int(ignore_index))
+
+
+def _merged_labels(loss_type, prediction_labels, retrieval_labels):
+    """The reference's seven RAVQA_loss_type rules (:942-1000) -> (merged_labels f32, ignore_mask bool), both [B, n_docs]."""
+    pred, ret = prediction_labels, retrieval_labels != 0
+    either, both = (pred | ret).float(), (pred & ret).float()
+    if loss_type == "Approach1":
+        return either, either == 0
+    if loss_type == "Approach2":
+        return either, pred & ~ret
+    if loss_type == "Approach3":
+        return either, ~ret
+    if loss_type == "Approach4":
+        return retrieval_labels, pred & ~ret
+    if loss_type == "Approach5":
+        return both, both == 0
+    if loss_type == "Approach6":
+        return both, pred ^ ret
+    if loss_type == "NoPR":
+        return pred.float(), torch.zeros_like(pred)
+    raise ValueError(f"loss_type must be one of {LOSS_TYPES}, got {loss_type!r}")
+
+
+def marginalised_loss(seq_logits, doc_scores, target, n_docs, bos_token_id=None, ignore_index=-100, retrieval_labels=None,
+                      loss_type=None, reduce_loss=True, want=LOSS_NAMES):
+    """`RagModelForBlip.get_loss` (rag_model_blip.py:826-1026): seq_logits [B * n_docs, T, V], doc_scores [B, n_docs] (what
+    retrieve_and_rescore returns, with its gradient to Q), target [B * n_docs, T] -> a dict with the keys named in `want`:
+
+      nll_loss         -ll [B, n_docs, T]; with reduce_loss its sum over the count of positions that are not ignore_index;
+      rag_loss         -sum_b logsumexp_d (sum_t ll[b, d, t] + log_softmax(doc_scores)[b, d]), the document term dropped where
+                       position p of (b, d) is ignored or p >= T; p = 1 when bos_token_id is given and every target row starts
+                       with it, else 0 (the position the reference adds doc_logprobs at, :866-874);
+      additional_loss  binary_cross_entropy(softmax(doc_scores), merged labels), masked, over its non-zero count (0 when that is
+                       0 or retrieval_labels is None); labels merged by `loss_type` (the model config's RAVQA_loss_type) from
+                       retrieval_labels [B, n_docs] and prediction_labels = (argmax of the first position's logits == the first
+                       target, which the reference reads as 0 where it is ignored and ignore_index < 0, :877-884, :933).
+
+    ll comes from token_log_likelihood, in fp32 whatever the logits' dtype; the rest is torch on [B, n_docs, T] or smaller (summed in
+    fp64, returned in fp32), and the gradient to doc_scores is plain autograd.  The reference fills the ignored entries of the caller's `target` with 0 in
+    place; here `target` is left as it was."""
+    unknown = [w for w in want if w not in LOSS_NAMES]
+    if unknown:
+        raise ValueError(f"want holds {unknown}; the losses are {LOSS_NAMES}")
+    n_docs = int(n_docs)
+    if seq_logits.dim() != 3 or n_docs < 1 or seq_logits.size(0) % n_docs:
+        raise ValueError(f"seq_logits {tuple(seq_logits.shape)} with n_docs = {n_docs}: expected [B * n_docs, T, V]")
+    R, T, _ = seq_logits.shape
+    B = R // n_docs
+    if tuple(doc_scores.shape) != (B, n_docs) or target.numel() != R * T:
+        raise ValueError(f"doc_scores {tuple(doc_scores.shape)} / target {tuple(target.shape)}: expected {(B, n_docs)} and {(R, T)}")
+    additional = "additional_loss" in want and retrieval_labels is not None
+    need_ll = "nll_loss" in want or "rag_loss" in want
+    out = {}
+    if need_ll or additional:
+        target = target.reshape(R, T).to(seq_logits.device)
+        ll, first_argmax = token_log_likelihood(seq_logits, target, ignore_index)
+        pad = (target == ignore_index).view(B, n_docs, T)
+        ll = ll.view(B, n_docs, T)
+    # past ll everything is small: the sums run in fp64 (their cost is nothing, and the posterior over documents -- the gradient
+    # that reaches Q -- then carries the rounding of ll alone); the results come back in ll's fp32
+    if "nll_loss" in want:
+        out["nll_loss"] = (-ll.double().sum() / (~pad).sum()).to(ll.dtype) if reduce_loss else -ll
+    if "rag_loss" in want:
+        use_bos = bos_token_id is not None and T > 0 and bool(target[:, 0].eq(bos_token_id).all())
+        p = 1 if use_bos else 0
+        seq_ll = ll.double().sum(2)
+        if p < T:
+            doc_logprobs = torch.log_softmax(doc_scores.to(ll.device).double(), dim=1)
+            seq_ll = seq_ll + doc_logprobs.masked_fill(pad[:, :, p], 0.0)
+        out["rag_loss"] = (-seq_ll.logsumexp(1).sum()).to(ll.dtype)
+    if "additional_loss" in want:
+        if not additional:
+            out["additional_loss"] = doc_scores.new_zeros(())
+        else:
+            first_target = target[:, 0]
+            if ignore_index < 0:
+                first_target = first_target.masked_fill(first_target == ignore_index, 0)
+            prediction_labels = (first_argmax == first_target).view(B, n_docs)
+            labels = torch.as_tensor(retrieval_labels).to(seq_logits.device).double().view(B, n_docs)
+            merged, ignore = _merged_labels(loss_type, prediction_labels, labels)
+            scores = doc_scores.to(seq_logits.device).double()
+            dist = torch.nn.functional.binary_cross_entropy(torch.softmax(scores, dim=-1), merged.double(), reduction="none")
+            dist = dist.masked_fill(ignore, 0.0)
+            # (count 0 means every entry is 0: the sum over max(count, 1) is then the reference's 0, without a host round trip)
+            out["additional_loss"] = (dist.sum() / torch.count_nonzero(dist).clamp(min=1)).to(doc_scores.dtype)
+    return out
