@@ -931,8 +931,8 @@ __device__ __forceinline__ void sel_pick_digit(const unsigned int* hist, int rem
     const int mine = h0 + h1 + h2 + h3;
     int incl = mine;  // inclusive suffix sum over lanes lane..63
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_down(incl, d, 64);
+    for (int d = 1; d < 64; d <<= 1) {   // (the source lane from `lane`, which callers hand in untraceable: __shfl_down's six lane
+        const int o = __builtin_amdgcn_ds_bpermute((lane + d) << 2, incl);   // addresses would each hold a register through the caller's loop)
         if (lane + d < 64) incl += o;
     }
     const int above = incl - mine;                  // keys in digits above this lane's group
@@ -947,13 +947,16 @@ __device__ __forceinline__ void sel_pick_digit(const unsigned int* hist, int rem
     }
     const unsigned long long m = __ballot(here);
     const int src = m ? __builtin_ctzll(m) : 0;
-    dsel = __shfl(d, src, 64); csel = __shfl(c, src, 64); rem_out = __shfl(r, src, 64);
+    dsel = __builtin_amdgcn_readlane(d, src); csel = __builtin_amdgcn_readlane(c, src); rem_out = __builtin_amdgcn_readlane(r, src);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Radix select: the n largest of count[q] 64-bit keys, unordered.  grid = nqueries, block = 1024.
 // Up to 8 passes of 8 bits from the top; the histogram lives in LDS; the leader digit of each wave is
 // aggregated with a ballot so the heavily repeated high bytes do not serialise on one LDS address.
+// The counts go to a [256 digits][32] array, lane l into column l & 31: a column is a bank, and lanes l and l + 32 are served
+// in different LDS cycles, so the increments of a wave neither queue on an address nor collide on a bank; after the counting
+// every thread folds a quarter of a row into the 256 counts the digit pick reads (fold()).
 // The first KPT * 1024 keys of a query are loaded ONCE into registers -- one block per query means one block per CU, so
 // a pass that re-reads global memory is pure exposed latency (30 dependent iterations x 9 passes before); only the tail
 // of longer lists streams from global memory in every pass.  The passes stop once the selected bucket is taken whole.
@@ -962,18 +965,20 @@ __device__ __forceinline__ void sel_pick_digit(const unsigned int* hist, int rem
 // keys carry upper-bound scores U; instead of the n largest, EVERY key whose score is >= (the n-th largest U) - band_err[q] is
 // emitted (no cap: out_stride >= count), and band_in[q] = how many -- the exact pass rescores them, the selection proper follows.
 // The other queries only copy their count to band_in.
+#define SEL_LIST_BYTES (4096 * 8)
 template <int KPT, bool BAND>
 __global__ __launch_bounds__(1024) void select_topn_kernel(const uint64_t* keys, int64_t key_stride,
                                                            const int32_t* counts, int32_t n, int32_t* out_pids,
                                                            int64_t out_stride, int32_t* n_out, uint64_t* out_keys,
                                                            uint64_t key_add, int32_t fixed_count, const int32_t* band_mode,
                                                            const float* band_err, int32_t* band_in) {
-    __shared__ unsigned int hist[256];
+    __shared__ unsigned int hist[256];                 // digit counts of the pass: the sums of hcol's rows
+    __shared__ __attribute__((aligned(16))) unsigned int hcol[256 * 32];   // [digit][lane & 31]: every lane counts in a bank of its own
     __shared__ unsigned long long s_prefix;
     __shared__ int s_remaining;
     __shared__ int s_out;
     __shared__ int s_done;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int P = counts ? counts[b] : fixed_count;
     const uint64_t* kb = keys + (size_t)b * key_stride;
     int32_t* ob = out_pids ? out_pids + (size_t)b * out_stride : nullptr;  // optional: the selected pids
@@ -1002,30 +1007,49 @@ __global__ __launch_bounds__(1024) void select_topn_kernel(const uint64_t* keys,
     for (int j = 0; j < KPT; j++) kreg[j] = (j * 1024 + tid < P) ? kb[j * 1024 + tid] : 0ull;
     // once the bucket that still has to be split holds <= SEL_LCAP keys they are copied to LDS and the remaining passes
     // touch nothing else
-    constexpr int SEL_LCAP = 4096;
-    __shared__ unsigned long long s_list[SEL_LCAP];
+    constexpr int SEL_LCAP = SEL_LIST_BYTES / 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned long long s_list[];   // SEL_LCAP keys (with hcol: past 64 KB, so dynamic)
     __shared__ int s_nlist, s_compact;
     if (tid == 0) { s_prefix = 0ull; s_remaining = n; s_out = 0; s_done = 0; s_nlist = 0; s_compact = 0; }
+    reinterpret_cast<uint4*>(hcol + 8 * tid)[0] = reinterpret_cast<uint4*>(hcol + 8 * tid)[1] = make_uint4(0u, 0u, 0u, 0u);
+    // after the counting: hist[d] = the sum of digit d's row, and the row is cleared for the next pass (thread t: a quarter of
+    // digit t >> 2's row)
+    auto fold = [&](int t) {
+        __syncthreads();
+        uint4* const hmine = reinterpret_cast<uint4*>(hcol + 8 * t);
+        const uint4 a = hmine[0], c = hmine[1];
+        hmine[0] = hmine[1] = make_uint4(0u, 0u, 0u, 0u);
+        unsigned int sum = a.x + a.y + a.z + a.w + c.x + c.y + c.z + c.w;
+        sum += (unsigned int)__builtin_amdgcn_mov_dpp((int)sum, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+        sum += (unsigned int)__builtin_amdgcn_mov_dpp((int)sum, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
+        if ((t & 3) == 0) hist[t >> 2] = sum;
+        __syncthreads();
+    };
     for (int pass = 0; pass < 8; pass++) {
         const int shift = 56 - 8 * pass;
-        if (tid < 256) hist[tid] = 0;
+        // the thread index as a value the compiler cannot trace: what derives from it (LDS addresses, the validity of every key
+        // slot) is recomputed where it is used and not carried in registers across the passes, next to KPT 64-bit keys
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        const int ln = t & 63;
+        const unsigned int hc = (unsigned int)ln & 31u;   // this lane's column = its bank (lanes l and l + 32 never meet in one LDS cycle)
         __syncthreads();
         if (s_done) break;  // block-uniform (written before the previous barrier pair)
         const unsigned long long prefix = s_prefix;
         if (s_compact) {  // block-uniform
             const int nl = s_nlist;
             for (int i0 = 0; i0 < nl; i0 += 1024) {
-                const int i = i0 + tid;
+                const int i = i0 + t;
                 const bool valid = i < nl;
                 const uint64_t key = valid ? s_list[i] : 0ull;
                 const bool act = valid && ((key >> (shift + 8)) == (prefix >> (shift + 8)));
-                if (act) atomicAdd(&hist[(unsigned int)(key >> shift) & 255u], 1u);
+                if (act) atomicAdd(&hcol[(((unsigned int)(key >> shift) & 255u) << 5) + hc], 1u);
             }
-            __syncthreads();
-            if (tid < 64) {
+            fold(t);
+            if (t < 64) {
                 int dsel, csel, rem;
-                sel_pick_digit(hist, s_remaining, lane, dsel, csel, rem);
-                if (tid == 0) {
+                sel_pick_digit(hist, s_remaining, ln, dsel, csel, rem);
+                if (t == 0) {
                     s_remaining = rem;
                     s_prefix = prefix | ((unsigned long long)dsel << shift);
                     if (csel == rem) s_done = 1;
@@ -1040,26 +1064,26 @@ __global__ __launch_bounds__(1024) void select_topn_kernel(const uint64_t* keys,
             const unsigned long long am = __ballot(act);
             if (am) {
                 const int leader = __builtin_ctzll(am);
-                const unsigned int ld = (unsigned int)__shfl((int)dg, leader, 64);
+                const unsigned int ld = (unsigned int)__builtin_amdgcn_readlane((int)dg, leader);
                 const unsigned long long same = __ballot(act && dg == ld);
-                if (lane == leader) atomicAdd(&hist[ld], (unsigned int)__popcll(same));
-                if (act && dg != ld) atomicAdd(&hist[dg], 1u);
+                if (ln == leader) atomicAdd(&hcol[(ld << 5) + hc], (unsigned int)__popcll(same));
+                if (act && dg != ld) atomicAdd(&hcol[(dg << 5) + hc], 1u);
             }
         };
 #pragma unroll
-        for (int j = 0; j < KPT; j++) count(j * 1024 + tid < P, kreg[j]);
+        for (int j = 0; j < KPT; j++) count(j * 1024 + t < P, kreg[j]);
         for (int i0 = KPT * 1024; i0 < P; i0 += 4 * 1024) {  // 4 loads in flight per thread: the tail is latency-bound too
             uint64_t kk[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + tid < P) ? kb[i0 + u * 1024 + tid] : 0ull;
+            for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + t < P) ? kb[i0 + u * 1024 + t] : 0ull;
 #pragma unroll
-            for (int u = 0; u < 4; u++) count(i0 + u * 1024 + tid < P, kk[u]);
+            for (int u = 0; u < 4; u++) count(i0 + u * 1024 + t < P, kk[u]);
         }
-        __syncthreads();
-        if (tid < 64) {
+        fold(t);
+        if (t < 64) {
             int dsel, csel, rem;
-            sel_pick_digit(hist, s_remaining, lane, dsel, csel, rem);
-            if (tid == 0) {
+            sel_pick_digit(hist, s_remaining, ln, dsel, csel, rem);
+            if (t == 0) {
                 s_remaining = rem;  // how many keys with the selected digit (and prefix) are still needed
                 s_prefix = prefix | ((unsigned long long)dsel << shift);
                 if (csel == rem) s_done = 1;  // the whole bucket is taken: every key >= the prefix (low bits 0) is selected
@@ -1069,17 +1093,18 @@ __global__ __launch_bounds__(1024) void select_topn_kernel(const uint64_t* keys,
         __syncthreads();
         if (s_compact && !s_done) {  // copy the bucket (keys whose top 8*(pass+1) bits equal the new prefix) to LDS
             const unsigned long long np = s_prefix;
+            asm volatile("" : "+v"(t));   // (as above: the counting's validity masks are not kept for this loop)
             auto take = [&](bool valid, uint64_t key) {
                 if (valid && ((key >> shift) == (np >> shift))) s_list[atomicAdd(&s_nlist, 1)] = key;
             };
 #pragma unroll
-            for (int j = 0; j < KPT; j++) take(j * 1024 + tid < P, kreg[j]);
+            for (int j = 0; j < KPT; j++) take(j * 1024 + t < P, kreg[j]);
             for (int i0 = KPT * 1024; i0 < P; i0 += 4 * 1024) {
                 uint64_t kk[4];
 #pragma unroll
-                for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + tid < P) ? kb[i0 + u * 1024 + tid] : 0ull;
+                for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + t < P) ? kb[i0 + u * 1024 + t] : 0ull;
 #pragma unroll
-                for (int u = 0; u < 4; u++) take(i0 + u * 1024 + tid < P, kk[u]);
+                for (int u = 0; u < 4; u++) take(i0 + u * 1024 + t < P, kk[u]);
             }
             // (the barrier at the top of the next pass orders these writes before the list is read)
         }
@@ -1111,20 +1136,22 @@ __global__ __launch_bounds__(1024) void select_topn_kernel(const uint64_t* keys,
         if (tid == 0) { n_out[b] = total; band_in[b] = total; }
         return;
     }
+    int tq = tid;   // (untraceable again, here and before the emit: see the pass loop)
+    asm volatile("" : "+v"(tq));
     int mine_gt = 0, mine_eq = 0;
 #pragma unroll
     for (int j = 0; j < KPT; j++) {
-        const bool v = j * 1024 + tid < P;
+        const bool v = j * 1024 + tq < P;
         mine_gt += (v && kreg[j] > thr) ? 1 : 0;
         mine_eq += (v && kreg[j] == thr) ? 1 : 0;
     }
     for (int i0 = KPT * 1024; i0 < P; i0 += 4 * 1024) {  // (the tail: 4 loads in flight)
         uint64_t kk[4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + tid < P) ? kb[i0 + u * 1024 + tid] : 0ull;
+        for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + tq < P) ? kb[i0 + u * 1024 + tq] : 0ull;
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const bool v = i0 + u * 1024 + tid < P;
+            const bool v = i0 + u * 1024 + tq < P;
             mine_gt += (v && kk[u] > thr) ? 1 : 0;
             mine_eq += (v && kk[u] == thr) ? 1 : 0;
         }
@@ -1133,6 +1160,7 @@ __global__ __launch_bounds__(1024) void select_topn_kernel(const uint64_t* keys,
     int pos_gt = flmr_block_exclusive_scan(mine_gt, sel_scan, &total_gt);
     __syncthreads();
     int pos_eq = total_gt + flmr_block_exclusive_scan(mine_eq, sel_scan, &total_eq);
+    asm volatile("" : "+v"(tq));
     auto emit = [&](bool valid, uint64_t key) {
         if (valid && key >= thr) {
             const int pos = key > thr ? pos_gt++ : pos_eq++;
@@ -1140,15 +1168,25 @@ __global__ __launch_bounds__(1024) void select_topn_kernel(const uint64_t* keys,
         }
     };
 #pragma unroll
-    for (int j = 0; j < KPT; j++) emit(j * 1024 + tid < P, kreg[j]);
+    for (int j = 0; j < KPT; j++) emit(j * 1024 + tq < P, kreg[j]);
     for (int i0 = KPT * 1024; i0 < P; i0 += 4 * 1024) {
         uint64_t kk[4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + tid < P) ? kb[i0 + u * 1024 + tid] : 0ull;
+        for (int u = 0; u < 4; u++) kk[u] = (i0 + u * 1024 + tq < P) ? kb[i0 + u * 1024 + tq] : 0ull;
 #pragma unroll
-        for (int u = 0; u < 4; u++) emit(i0 + u * 1024 + tid < P, kk[u]);
+        for (int u = 0; u < 4; u++) emit(i0 + u * 1024 + tq < P, kk[u]);
     }
     if (tid == 0 && n_out) n_out[b] = (total_gt + total_eq) < n ? (total_gt + total_eq) : n;
+}
+
+// (the bucket list is dynamic LDS: beside the histogram columns the kernel's LDS passes 64 KB, which a launch has to be allowed)
+template <int KPT, bool BAND, typename... Args>
+static int sel_launch(int32_t nqueries, hipStream_t st, Args... args) {
+    FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_topn_kernel<KPT, BAND>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 SEL_LIST_BYTES));
+    hipLaunchKernelGGL((select_topn_kernel<KPT, BAND>), dim3(nqueries), dim3(1024), SEL_LIST_BYTES, st, args...);
+    FLMR_LAUNCH_CHECK();
+    return FLMR_OK;
 }
 
 int flmr_launch_select_topn(const uint64_t* keys, int64_t key_stride, const int32_t* counts, int32_t nqueries,
@@ -1156,38 +1194,29 @@ int flmr_launch_select_topn(const uint64_t* keys, int64_t key_stride, const int3
                             uint64_t* out_keys, uint64_t key_add) {
     // keys per thread held in registers: sized from the candidate capacity (the tail of longer lists streams)
     if (key_stride <= 16 * 1024)
-        hipLaunchKernelGGL((select_topn_kernel<16, false>), dim3(nqueries), dim3(1024), 0, st, keys, key_stride, counts, n, out_pids,
-                           out_stride, n_out, out_keys, key_add, 0, nullptr, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((select_topn_kernel<24, false>), dim3(nqueries), dim3(1024), 0, st, keys, key_stride, counts, n, out_pids,
-                           out_stride, n_out, out_keys, key_add, 0, nullptr, nullptr, nullptr);
-    FLMR_LAUNCH_CHECK();
-    return FLMR_OK;
+        return sel_launch<16, false>(nqueries, st, keys, key_stride, counts, n, out_pids, out_stride, n_out, out_keys, key_add, 0, nullptr,
+                                     nullptr, nullptr);
+    return sel_launch<24, false>(nqueries, st, keys, key_stride, counts, n, out_pids, out_stride, n_out, out_keys, key_add, 0, nullptr,
+                                 nullptr, nullptr);
 }
 
 int flmr_launch_s1_band(const uint64_t* keys, int64_t key_stride, const int32_t* counts, const int32_t* mode, const float* err,
                         int32_t nqueries, int32_t n, int32_t* band, int32_t* band_count, int32_t* in_count, hipStream_t st) {
     if (key_stride <= 16 * 1024)
-        hipLaunchKernelGGL((select_topn_kernel<16, true>), dim3(nqueries), dim3(1024), 0, st, keys, key_stride, counts, n, band,
-                           key_stride, band_count, nullptr, 0ull, 0, mode, err, in_count);
-    else
-        hipLaunchKernelGGL((select_topn_kernel<24, true>), dim3(nqueries), dim3(1024), 0, st, keys, key_stride, counts, n, band,
-                           key_stride, band_count, nullptr, 0ull, 0, mode, err, in_count);
-    FLMR_LAUNCH_CHECK();
-    return FLMR_OK;
+        return sel_launch<16, true>(nqueries, st, keys, key_stride, counts, n, band, key_stride, band_count, nullptr, 0ull, 0, mode, err,
+                                    in_count);
+    return sel_launch<24, true>(nqueries, st, keys, key_stride, counts, n, band, key_stride, band_count, nullptr, 0ull, 0, mode, err,
+                                in_count);
 }
 
 // keys [nqueries, m] (0 = empty) -> the n largest of each row, UNORDERED, 0 padded (exchange steps of the sharded protocol
 // whose consumers do not care about order: a radix select instead of a full bitonic sort of up to 8192 keys)
 int flmr_launch_select_keys(const uint64_t* keys, int32_t nqueries, int32_t m, int32_t n, uint64_t* out, hipStream_t st) {
     if (m <= 16 * 1024)
-        hipLaunchKernelGGL((select_topn_kernel<16, false>), dim3(nqueries), dim3(1024), 0, st, keys, (int64_t)m, nullptr, n, nullptr,
-                           (int64_t)n, nullptr, out, 0ull, m, nullptr, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((select_topn_kernel<24, false>), dim3(nqueries), dim3(1024), 0, st, keys, (int64_t)m, nullptr, n, nullptr,
-                           (int64_t)n, nullptr, out, 0ull, m, nullptr, nullptr, nullptr);
-    FLMR_LAUNCH_CHECK();
-    return FLMR_OK;
+        return sel_launch<16, false>(nqueries, st, keys, (int64_t)m, nullptr, n, nullptr, (int64_t)n, nullptr, out, 0ull, m, nullptr, nullptr,
+                                     nullptr);
+    return sel_launch<24, false>(nqueries, st, keys, (int64_t)m, nullptr, n, nullptr, (int64_t)n, nullptr, out, 0ull, m, nullptr, nullptr,
+                                 nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
