@@ -71,6 +71,28 @@ int flmr_process_options(flmr_options* out);
 static inline int64_t flmr_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t flmr_round_up(int64_t a, int64_t b) { return flmr_ceil_div(a, b) * b; }
 
+// ---- the argument rules of the MaxSim entry points (padded, typed, gathered, index; forward and backward) -------------------
+// One statement of each rule, INVALID before UNSUPPORTED.  An entry point keeps only what is its own (NULL pointers, dtypes,
+// which sizes it has, where an empty batch returns) and switches a rule off by passing the value that satisfies it:
+//   q_batch, B, cross   the padded forms' query rule: q_batch is 1 or B; the cross form takes 1..65535 queries (a grid dimension).
+//                       Off: 1, 1, 0
+//   sizes_ok            the entry point's own sizes are in range.  Off: true
+//   ptrs                OR of the pointers whose rows are read 16 bytes at a time.  Off: 0
+//   dim                 the build's embedding width.  Off: FLMR_DIM
+//   nq, nq_max          the query columns whose state the kernel keeps in LDS.  Off: FLMR_MAXSIM_NQ_ANY
+#define FLMR_MAXSIM_NQ_KEYS ((size_t)64 * 1024 / 8)   // 8-byte (value, ~token) keys in 64 KiB
+#define FLMR_MAXSIM_NQ_ANY (~(size_t)0)
+static inline int flmr_maxsim_check(int32_t q_batch, int32_t B, int32_t cross, bool sizes_ok, uintptr_t ptrs, int32_t dim, int32_t nq,
+                                    size_t nq_max) {
+    if (!cross && q_batch != 1 && q_batch != B) FLMR_FAIL(FLMR_ERR_INVALID, "q_batch must be 1 or B");
+    if (cross && (q_batch < 1 || q_batch > 65535)) FLMR_FAIL(FLMR_ERR_INVALID, "cross scoring takes 1..65535 queries per call");
+    if (!sizes_ok) FLMR_FAIL(FLMR_ERR_INVALID, "bad sizes");
+    if (ptrs & 15) FLMR_FAIL(FLMR_ERR_INVALID, "the query, document and gradient rows must be 16-byte aligned");
+    if (dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dim=%d (this build: %d)", dim, FLMR_DIM);
+    if ((size_t)nq > nq_max) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
+    return FLMR_OK;
+}
+
 // ---- (score, pid) keys -----------------------------------------------------------------------
 // The reference selects with std::priority_queue<std::pair<float,int>> (filter_pids.cpp:24): descending
 // lexicographic (score, pid).  A 64-bit key whose unsigned order equals that order lets one integer

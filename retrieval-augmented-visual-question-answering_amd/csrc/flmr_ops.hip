@@ -6,7 +6,7 @@
 //   colbert_score (padded)    TPC/modeling/colbert.py:235-286
 // These exist so each stage can be parity-tested in isolation and slotted behind the reference's class
 // attributes (IndexScorer.filter_pids, ...).  The batched search path (flmr_search.hip) does not use them.
-#include "flmr_device.h"
+#include "flmr_maxsim_tile.h"
 
 // RAII-less scratch helper: ops allocate small temporaries and free them after a stream sync.
 struct scratch {
@@ -272,10 +272,6 @@ __global__ __launch_bounds__(256) void colbert_score_padded_kernel(const float* 
 // 32-token tiles; both operands are split into fp16 hi/lo on the fly (D rows per tile, Q once per call by
 // score_split_q) and contracted with three v_mfma_f32_32x32x16_f16 per 16 dims (hi.hi + 2^-11 (hi.lo + lo.hi), fp32
 // accumulation, ~2^-21 relative error per term).  Query chunks of 128 rows are staged in LDS and shared by the waves.
-typedef _Float16 ph8 __attribute__((ext_vector_type(8)));
-#define PS_QC 4
-#define PS_BROW 136
-
 __global__ __launch_bounds__(256) void score_split_q(const float* Q, int rows, int nq, int nqp, _Float16* q_hi, _Float16* q_lo) {
     // Q [q_batch, nq, 128] -> hi/lo [q_batch, nqp, 128], rows >= nq zero
     const size_t total = (size_t)rows * nqp * FLMR_DIM;
@@ -290,13 +286,9 @@ __global__ __launch_bounds__(256) void score_split_q(const float* Q, int rows, i
 }
 
 // ARGMAX (the autograd forward, flmr_colbert_maxsim_fwd): the same arithmetic, plus the winning token of every column in
-// argmax_out i32 [rows, nq] (-1: padded winner or Ld == 0).  Each lane carries (value, token) through its 16 rows and the
-// half-wave exchange; the LDS column maximum becomes the 64-bit key f2ord(v) << 32 | ~token, whose high word is exactly the
-// fp32 column maximum of the plain instantiation and whose low word makes ties go to the LOWEST token, as torch's max(dim)
-// does under autograd.  That instantiation reads fp32 Q and splits it while staging (the same hi/lo values score_split_q
-// writes), so it needs no workspace and no host synchronisation.
-// TWIN: maxsim_gather_fwd_kernel (flmr_rescore.hip) is this instantiation with the document taken from a passage store by pid;
-// a fix to the tile walk, the key or the tie rule here must be made there too (tests/test_rag_rescore_gpu.py asserts bit-identity).
+// argmax_out i32 [rows, nq] (-1: padded winner or Ld == 0), carried through the fold as the (value, ~token) key.  That
+// instantiation reads fp32 Q and splits it while staging (the same hi/lo values score_split_q writes), so it needs no workspace
+// and no host synchronisation.  The tile body is flmr_maxsim_tile.h's, shared with the gathered and the half-precision kernels.
 template <bool ARGMAX>
 __global__ __launch_bounds__(256, 2) void colbert_score_padded_mfma_kernel(const _Float16* __restrict__ q_hi,
                                                                            const _Float16* __restrict__ q_lo,
@@ -305,132 +297,48 @@ __global__ __launch_bounds__(256, 2) void colbert_score_padded_mfma_kernel(const
                                                                            const uint8_t* __restrict__ mask, int Ld,
                                                                            float* out, float* colmax_out, int32_t* argmax_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* bq = reinterpret_cast<_Float16*>(smem);                                          // [PS_QC][hi|lo][32][PS_BROW]
-    unsigned int* colmax = reinterpret_cast<unsigned int*>(bq + PS_QC * 2 * 32 * PS_BROW);     // [nqp] order-preserving fp32 image
-    unsigned long long* colkey = reinterpret_cast<unsigned long long*>(colmax);                 // ARGMAX: [nqp] (value, ~token)
+    _Float16* bq = reinterpret_cast<_Float16*>(smem);                                            // [MT_QC][hi|lo][32][MT_BROW]
+    mt_col_t<ARGMAX>* cols = reinterpret_cast<mt_col_t<ARGMAX>*>(bq + MT_QC * 2 * 32 * MT_BROW);   // [nqp] column state
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
     // gridDim.y > 1: the CROSS form -- every query (blockIdx.y) against every document, out [gridDim.y, B]
     const size_t ob = (size_t)blockIdx.y * gridDim.x + b;
     const size_t qoff = (gridDim.y > 1 ? (size_t)blockIdx.y : (q_batch == 1 ? 0 : (size_t)b)) * nqp * FLMR_DIM;
-    for (int k = tid; k < nqp; k += 256) {  // below every real value
-        if constexpr (ARGMAX) colkey[k] = 0ull;
-        else colmax[k] = 0u;
-    }
+    for (int k = tid; k < nqp; k += 256) cols[k] = 0;   // below every real value
     const int ntiles = (Ld + 31) >> 5;
-    for (int qc0 = 0; qc0 < nq; qc0 += 32 * PS_QC) {
-        const int ntq = ((nq - qc0 < 32 * PS_QC ? nq - qc0 : 32 * PS_QC) + 31) >> 5;
+    for (int qc0 = 0; qc0 < nq; qc0 += 32 * MT_QC) {
+        const int ntq = mt_chunk_tiles(nq, qc0);
         __syncthreads();
-        if constexpr (ARGMAX) {   // fp32 Q [rows, nq, 128] split on the fly; rows >= nq stage as zero (score_split_q's rule)
-            const size_t qrow0 = qoff / ((size_t)nqp * FLMR_DIM) * nq;
-            for (int e = tid; e < ntq * 512; e += 256) {
-                const int piece = e & 15, row = (e >> 4) & 31, qt = e >> 9, r = qc0 + qt * 32 + row;
-                ph8 hi8, lo8;
-                if (r < nq) {
-                    const float4* src = reinterpret_cast<const float4*>(Qf + (qrow0 + r) * FLMR_DIM + piece * 8);
-                    const float4 x = src[0], y = src[1];
-                    const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        const _Float16 hi = (_Float16)v[k];
-                        hi8[k] = hi;
-                        lo8[k] = (_Float16)((v[k] - (float)hi) * 2048.0f);
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; k++) { hi8[k] = (_Float16)0.0f; lo8[k] = (_Float16)0.0f; }
-                }
-                *reinterpret_cast<ph8*>(bq + ((qt * 2 + 0) * 32 + row) * PS_BROW + piece * 8) = hi8;
-                *reinterpret_cast<ph8*>(bq + ((qt * 2 + 1) * 32 + row) * PS_BROW + piece * 8) = lo8;
-            }
+        if constexpr (ARGMAX) {   // fp32 Q [rows, nq, 128] split on the fly
+            mt_stage_q_f32(bq, Qf, qoff / ((size_t)nqp * FLMR_DIM) * nq, qc0, ntq, nq, tid);
         } else {
             for (int e = tid; e < ntq * 1024; e += 256) {
                 const int piece = e & 15, row = (e >> 4) & 31, hl = (e >> 9) & 1, qt = e >> 10;
                 const _Float16* src = (hl ? q_lo : q_hi) + qoff + (size_t)(qc0 + qt * 32 + row) * FLMR_DIM + piece * 8;
-                *reinterpret_cast<ph8*>(bq + ((qt * 2 + hl) * 32 + row) * PS_BROW + piece * 8) = *reinterpret_cast<const ph8*>(src);
+                *reinterpret_cast<f16x8*>(bq + ((qt * 2 + hl) * 32 + row) * MT_BROW + piece * 8) = *reinterpret_cast<const f16x8*>(src);
             }
         }
         __syncthreads();
         for (int t = wave; t < ntiles; t += 4) {
             const int tok = t * 32 + i;
             const bool inb = tok < Ld;
-            ph8 ah[8], al[8];
-            {
-                const float4* p = reinterpret_cast<const float4*>(D + ((size_t)b * Ld + (inb ? tok : 0)) * FLMR_DIM + 64 * h);
-#pragma unroll
-                for (int s = 0; s < 8; s++) {
-                    const float4 x = p[2 * s], y = p[2 * s + 1];
-                    const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        const _Float16 hi = (_Float16)v[e];
-                        ah[s][e] = hi;
-                        al[s][e] = (_Float16)((v[e] - (float)hi) * 2048.0f);
-                    }
-                }
-            }
-            // which of this lane's 16 accumulator rows are real, unmasked tokens (bit r)
-            uint32_t okbits = 0;
+            f16x8 ah[8], al[8];
+            mt_load_row_f32(D + ((size_t)b * Ld + (inb ? tok : 0)) * FLMR_DIM + 64 * h, ah, al);
+            uint32_t okbits = 0;   // which of this lane's 16 accumulator rows are real, unmasked tokens (bit r)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mt_row(t, r, h);
                 if (row < Ld && mask[(size_t)b * Ld + row]) okbits |= 1u << r;
             }
             for (int qt = 0; qt < ntq; qt++) {
                 f32x16 acch, accl, accm;
-#pragma unroll
-                for (int r = 0; r < 16; r++) { acch[r] = 0.0f; accl[r] = 0.0f; accm[r] = 0.0f; }
-#pragma unroll
-                for (int s = 0; s < 8; s++) {
-                    const ph8 bh = *reinterpret_cast<const ph8*>(bq + ((qt * 2 + 0) * 32 + i) * PS_BROW + 64 * h + 8 * s);
-                    const ph8 bl = *reinterpret_cast<const ph8*>(bq + ((qt * 2 + 1) * 32 + i) * PS_BROW + 64 * h + 8 * s);
-                    acch = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh, acch, 0, 0, 0);
-                    accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl, accl, 0, 0, 0);
-                    accm = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh, accm, 0, 0, 0);
-                }
-                float mx = FLMR_NEG_INF;
-                int arg = 0x7fffffff;   // ARGMAX: the lowest row holding mx (rows ascend with r for a fixed h)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float v = ((okbits >> r) & 1u) ? fmaf(accl[r] + accm[r], 1.0f / 2048.0f, acch[r]) : -9999.0f;  // colbert.py:240
-                    if constexpr (ARGMAX) {
-                        if (row < Ld && v > mx) { mx = v; arg = row; }
-                    } else {
-                        if (row < Ld) mx = fmaxf(mx, v);
-                    }
-                }
-                const int col = qc0 + qt * 32 + i;
-                if constexpr (ARGMAX) {
-                    const float omx = __shfl_xor(mx, 32, 64);
-                    const int oarg = __shfl_xor(arg, 32, 64);
-                    if (omx > mx || (omx == mx && oarg < arg)) { mx = omx; arg = oarg; }
-                    if (h == 0 && col < nq && mx > FLMR_NEG_INF)
-                        atomicMax(&colkey[col], ((unsigned long long)flmr_f2ord(mx) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)arg));
-                } else {
-                    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                    if (h == 0 && col < nq && mx > FLMR_NEG_INF) atomicMax(&colmax[col], flmr_f2ord(mx));
-                }
+                mt_products<true, true>(bq, qt, i, h, ah, al, acch, accl, accm);
+                mt_fold<ARGMAX>(acch, accl, accm, okbits, t, h, Ld, qc0 + qt * 32 + i, nq, cols);
             }
         }
     }
     __syncthreads();
-    auto cmax = [&](int k) -> float {
-        if constexpr (ARGMAX) return (Ld > 0) ? flmr_ord2f((unsigned int)(colkey[k] >> 32)) : FLMR_NEG_INF;
-        else return (Ld > 0) ? flmr_ord2f(colmax[k]) : FLMR_NEG_INF;
-    };
-    if constexpr (ARGMAX)
-        for (int k = tid; k < nq; k += 256) {
-            const int tok = (Ld > 0) ? (int)(0xFFFFFFFFu - (uint32_t)colkey[k]) : -1;
-            argmax_out[ob * nq + k] = (tok >= 0 && mask[(size_t)b * Ld + tok]) ? tok : -1;
-        }
-    if (colmax_out)
-        for (int k = tid; k < nq; k += 256) colmax_out[ob * nq + k] = cmax(k);
-    if (tid == 0 && out) {
-        float sc = 0.0f;
-        for (int k = 0; k < nq; k++) sc += cmax(k);
-        out[ob] = sc;
-    }
+    mt_epilogue<ARGMAX>(cols, Ld > 0, [=](int tok) { return mask[(size_t)b * Ld + tok]; }, ob, nq, tid, out, colmax_out, argmax_out);
 }
 
 // cross: Q holds q_batch independent queries and EVERY one of them is scored against every document (out [q_batch, B])
@@ -446,22 +354,21 @@ static int score_form_of(int32_t dim, score_form* form) {
 static int score_padded_form(score_form form, const float* Q, int32_t q_batch, int32_t nq, const float* D, const uint8_t* mask,
                              int32_t B, int32_t Ld, int32_t dim, float* out, float* colmax_out, flmr_stream_t stream, bool cross) {
     if (!Q || !D || !mask || (!out && !colmax_out)) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    if (!cross && q_batch != 1 && q_batch != B) FLMR_FAIL(FLMR_ERR_INVALID, "q_batch must be 1 or B");
-    if (cross && (q_batch < 1 || q_batch > 65535)) FLMR_FAIL(FLMR_ERR_INVALID, "cross scoring takes 1..65535 queries per call");
+    RUN(flmr_maxsim_check(q_batch, B, cross, true, 0, FLMR_DIM, nq, FLMR_MAXSIM_NQ_ANY));   // the query rule; an empty batch returns before the limits
     if (B <= 0) return FLMR_OK;
     const dim3 grid((unsigned)B, cross ? (unsigned)q_batch : 1u);
     if (cross && q_batch == 1) cross = false;   // (the broadcast form)
-    if ((size_t)nq * 4 > 48 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
+    // 4-byte column maxima in the 48 KiB a kernel has without opting in; the plain-FMA form takes any dim
+    RUN(flmr_maxsim_check(1, 1, 0, true, 0, form == score_form::mfma ? dim : FLMR_DIM, nq, 48 * 1024 / 4));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (form == score_form::mfma) {
-        if (dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the MFMA scorer needs dim == %d", FLMR_DIM);
         scratch sc;
         const int nqp = (int)flmr_round_up(nq, 32);
         _Float16 *qh, *ql;
         RUN(sc.alloc(&qh, (size_t)q_batch * nqp * FLMR_DIM));
         RUN(sc.alloc(&ql, (size_t)q_batch * nqp * FLMR_DIM));
         hipLaunchKernelGGL(score_split_q, dim3(1024), dim3(256), 0, st, Q, q_batch, nq, nqp, qh, ql);
-        const size_t lds = (size_t)PS_QC * 2 * 32 * PS_BROW * sizeof(_Float16) + (size_t)nqp * sizeof(unsigned int);
+        const size_t lds = mt_stage_bytes<2>() + (size_t)nqp * sizeof(unsigned int);
         FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_padded_mfma_kernel<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(colbert_score_padded_mfma_kernel<false>, grid, dim3(256), lds, st, qh, ql, nullptr, q_batch, nq, nqp, D,
@@ -510,16 +417,12 @@ extern "C" int flmr_colbert_maxsim_fwd(const float* Q, int32_t q_batch, int32_t 
                                        int32_t B, int32_t Ld, int32_t dim, int32_t cross, float* out, float* colmax,
                                        int32_t* argmax, flmr_stream_t stream) {
     if (!Q || !D || !mask || !argmax) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    if (!cross && q_batch != 1 && q_batch != B) FLMR_FAIL(FLMR_ERR_INVALID, "q_batch must be 1 or B");
-    if (cross && (q_batch < 1 || q_batch > 65535)) FLMR_FAIL(FLMR_ERR_INVALID, "cross scoring takes 1..65535 queries per call");
-    if (nq < 1 || B < 0 || Ld < 0) FLMR_FAIL(FLMR_ERR_INVALID, "bad sizes");
-    if (dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dim=%d (this build: %d)", dim, FLMR_DIM);
-    if ((size_t)nq * 8 > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
+    RUN(flmr_maxsim_check(q_batch, B, cross, nq >= 1 && B >= 0 && Ld >= 0, 0, dim, nq, FLMR_MAXSIM_NQ_KEYS));
     if (B == 0) return FLMR_OK;
     const dim3 grid((unsigned)B, cross ? (unsigned)q_batch : 1u);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nqp = (int)flmr_round_up(nq, 32);
-    const size_t lds = (size_t)PS_QC * 2 * 32 * PS_BROW * sizeof(_Float16) + (size_t)nqp * sizeof(unsigned long long);
+    const size_t lds = mt_stage_bytes<2>() + (size_t)nqp * sizeof(unsigned long long);
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_padded_mfma_kernel<true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(colbert_score_padded_mfma_kernel<true>, grid, dim3(256), lds, st, nullptr, nullptr, Q, q_batch, nq, nqp,

@@ -2,12 +2,12 @@
 // under autograd, flmr_maxsim_gather_fwd / _bwd.
 //
 // Output row r = q * k + j scores query q against passage pids[q, j] of a device-resident store [npassages, Ld, 128] (fp32 or
-// fp16) with mask [npassages, Ld].  The forward is colbert_score_padded_mfma_kernel<true> (flmr_ops.hip) with the document base
-// taken from the pid and the query block from r / k: the same staging of Q, the same tile walk, the same accumulation and the
-// same (value, ~token) LDS key, so out / colmax / argmax are bit-identical to flmr_colbert_maxsim_fwd on
-// Q.repeat_interleave(k) and store[pids] -- neither of which is ever built.  An fp16 store value has a zero low part, so the
-// third product of the split (lo(D) x hi(Q)) is identically +0 and is not issued: two MFMAs per 16 dims instead of three and
-// half the bytes per token row, with the same bits as the fp32 kernel gives the widened values.
+// fp16) with mask [npassages, Ld].  The forward runs the tile body of flmr_maxsim_tile.h -- the one
+// colbert_score_padded_mfma_kernel<true> (flmr_ops.hip) runs: staging of Q, tile walk, accumulation, (value, ~token) LDS key --
+// with the document base taken from the pid and the query block from r / k, so out / colmax / argmax are bit-identical to
+// flmr_colbert_maxsim_fwd on Q.repeat_interleave(k) and store[pids] -- neither of which is ever built.  An fp16 store value has
+// a zero low part, so the third product of the split (lo(D) x hi(Q)) is identically +0 and is not issued: two MFMAs per 16 dims
+// instead of three and half the bytes per token row, with the same bits as the fp32 kernel gives the widened values.
 // The backward writes dQ alone (the store is a constant of training): one wave per (q, i), the k rows of the query walked in
 // ascending j -- a fixed order, no floating-point atomics.
 //
@@ -16,12 +16,9 @@
 // or the index at nbits 1 / 2 / 4 / 8, whose loader decodes a lane's half row (code -> centroid half-row, 8 * nbits residual
 // bytes -> bucket weights), normalises it and splits it into the fp16 hi / lo operand.  Passage p's tokens are
 // doc_offsets[p] .. doc_offsets[p + 1]: no mask array, no common padded length, no uncompressed copy of the corpus.
-#include "flmr_device.h"
+#include "flmr_maxsim_tile.h"
 
-typedef _Float16 rh8 __attribute__((ext_vector_type(8)));
 typedef _Float16 rh2 __attribute__((ext_vector_type(2)));
-#define RS_QC 4        // query tiles of 32 rows staged per pass (as PS_QC)
-#define RS_BROW 136    // LDS row pitch in halves (as PS_BROW)
 
 // ---- document-row loaders -------------------------------------------------------------------------------------------
 // What the two kernels ask of a loader L (passed by value as a kernel argument):
@@ -60,26 +57,10 @@ struct rs_store_loader {
         return d;
     }
     __device__ __forceinline__ bool ok(const rs_doc& d, int row) const { return d.mrow[row] != 0; }
-    __device__ __forceinline__ void load(const rs_doc& d, const char*, int tok, int h, rh8 (&ah)[8], rh8 (&al)[8]) const {
+    __device__ __forceinline__ void load(const rs_doc& d, const char*, int tok, int h, f16x8 (&ah)[8], f16x8 (&al)[8]) const {
         const size_t drow = (d.base + (tok < Ld ? tok : 0)) * FLMR_DIM + 64 * h;   // (rows past Ld re-read token 0)
-        if constexpr (F16) {
-            const rh8* p = reinterpret_cast<const rh8*>(reinterpret_cast<const _Float16*>(store) + drow);
-#pragma unroll
-            for (int s = 0; s < 8; s++) ah[s] = p[s];
-        } else {
-            const float4* p = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(store) + drow);
-#pragma unroll
-            for (int s = 0; s < 8; s++) {
-                const float4 x = p[2 * s], y = p[2 * s + 1];
-                const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const _Float16 hi = (_Float16)v[e];
-                    ah[s][e] = hi;
-                    al[s][e] = (_Float16)((v[e] - (float)hi) * 2048.0f);
-                }
-            }
-        }
+        if constexpr (F16) mt_load_row_f16(reinterpret_cast<const _Float16*>(store) + drow, ah);
+        else mt_load_row_f32(reinterpret_cast<const float*>(store) + drow, ah, al);
     }
     __device__ __forceinline__ bool row2(int p, int a, int lane, float2& d) const {
         if (a < 0 || a >= Ld || p < 0 || p >= npassages) return false;
@@ -150,7 +131,7 @@ struct rs_index_loader {
             w[0] = tab[byte];
         }
     }
-    __device__ __forceinline__ void load(const rs_doc& d, const char* lds, int tok, int h, rh8 (&ah)[8], rh8 (&al)[8]) const {
+    __device__ __forceinline__ void load(const rs_doc& d, const char* lds, int tok, int h, f16x8 (&ah)[8], f16x8 (&al)[8]) const {
         const float* tab = reinterpret_cast<const float*>(lds);
         const size_t tc = d.base + (tok < d.len ? tok : 0);   // (rows past the passage end re-read token 0)
         const float4* c4 = reinterpret_cast<const float4*>(centroids + (size_t)code_of(tc) * FLMR_DIM + 64 * h);
@@ -184,13 +165,10 @@ struct rs_index_loader {
         const float inv = 1.0f / nrm;
 #pragma unroll
         for (int s = 0; s < 8; s++) {
+            float v[8];
 #pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const float v = x[8 * s + e] * inv;
-                const _Float16 hi = (_Float16)v;
-                ah[s][e] = hi;
-                al[s][e] = (_Float16)((v - (float)hi) * 2048.0f);
-            }
+            for (int e = 0; e < 8; e++) v[e] = x[8 * s + e] * inv;
+            mt_split8(v, ah[s], al[s]);
         }
     }
     // the winner row decoded on the fly: the lane's two dims share a residual byte (two bytes at nbits 8); the norm is the wave's
@@ -224,13 +202,14 @@ struct rs_index_loader {
     }
 };
 
+// The ARGMAX tile body of flmr_maxsim_tile.h with the document taken from loader L by pid and the query block from row / k.
 template <class L>
 __global__ __launch_bounds__(256, 2) void maxsim_gather_fwd_kernel(const float* __restrict__ Qf, int nq, int nqp, const L ld,
                                                                    const int32_t* __restrict__ pids, int k,
                                                                    float* out, float* colmax_out, int32_t* argmax_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* bq = reinterpret_cast<_Float16*>(smem);                                                   // [RS_QC][hi|lo][32][RS_BROW]
-    unsigned long long* colkey = reinterpret_cast<unsigned long long*>(bq + RS_QC * 2 * 32 * RS_BROW);   // [nqp] (value, ~token)
+    _Float16* bq = reinterpret_cast<_Float16*>(smem);                                                   // [MT_QC][hi|lo][32][MT_BROW]
+    unsigned long long* colkey = reinterpret_cast<unsigned long long*>(bq + MT_QC * 2 * 32 * MT_BROW);   // [nqp] (value, ~token)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
     const size_t ob = blockIdx.x;
@@ -241,86 +220,33 @@ __global__ __launch_bounds__(256, 2) void maxsim_gather_fwd_kernel(const float* 
     const int Ld = doc.len;
     if (live) ld.stage(const_cast<char*>(ltab), tid);   // (ordered before the first tile by the barriers of the first pass)
     // what the tile walk leaves in a column of an all-padded document: -9999 held by token 0
-    const unsigned long long padkey = ((unsigned long long)flmr_f2ord(-9999.0f) << 32) | 0xFFFFFFFFull;
+    const unsigned long long padkey = mt_key(-9999.0f, 0);
     for (int c = tid; c < nqp; c += 256) colkey[c] = (!live && doc.cols && c < nq) ? padkey : 0ull;
     const int ntiles = live ? (Ld + 31) >> 5 : 0;
-    for (int qc0 = 0; qc0 < nq && live; qc0 += 32 * RS_QC) {
-        const int ntq = ((nq - qc0 < 32 * RS_QC ? nq - qc0 : 32 * RS_QC) + 31) >> 5;
+    for (int qc0 = 0; qc0 < nq && live; qc0 += 32 * MT_QC) {
+        const int ntq = mt_chunk_tiles(nq, qc0);
         __syncthreads();
-        for (int e = tid; e < ntq * 512; e += 256) {   // fp32 Q split on the fly; rows >= nq stage as zero
-            const int piece = e & 15, row = (e >> 4) & 31, qt = e >> 9, r = qc0 + qt * 32 + row;
-            rh8 hi8, lo8;
-            if (r < nq) {
-                const float4* src = reinterpret_cast<const float4*>(Qf + (qrow0 + r) * FLMR_DIM + piece * 8);
-                const float4 x = src[0], y = src[1];
-                const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-#pragma unroll
-                for (int d = 0; d < 8; d++) {
-                    const _Float16 hi = (_Float16)v[d];
-                    hi8[d] = hi;
-                    lo8[d] = (_Float16)((v[d] - (float)hi) * 2048.0f);
-                }
-            } else {
-#pragma unroll
-                for (int d = 0; d < 8; d++) { hi8[d] = (_Float16)0.0f; lo8[d] = (_Float16)0.0f; }
-            }
-            *reinterpret_cast<rh8*>(bq + ((qt * 2 + 0) * 32 + row) * RS_BROW + piece * 8) = hi8;
-            *reinterpret_cast<rh8*>(bq + ((qt * 2 + 1) * 32 + row) * RS_BROW + piece * 8) = lo8;
-        }
+        mt_stage_q_f32(bq, Qf, qrow0, qc0, ntq, nq, tid);   // fp32 Q split on the fly
         __syncthreads();
         for (int t = wave; t < ntiles; t += 4) {
             const int tok = t * 32 + i;
-            rh8 ah[8], al[8];
+            f16x8 ah[8], al[8];
             ld.load(doc, ltab, tok, h, ah, al);
             uint32_t okbits = 0;   // which of this lane's 16 accumulator rows are real, unmasked tokens (bit r)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mt_row(t, r, h);
                 if (row < Ld && ld.ok(doc, row)) okbits |= 1u << r;
             }
             for (int qt = 0; qt < ntq; qt++) {
                 f32x16 acch, accl, accm;
-#pragma unroll
-                for (int r = 0; r < 16; r++) { acch[r] = 0.0f; accl[r] = 0.0f; accm[r] = 0.0f; }
-#pragma unroll
-                for (int s = 0; s < 8; s++) {
-                    const rh8 bh = *reinterpret_cast<const rh8*>(bq + ((qt * 2 + 0) * 32 + i) * RS_BROW + 64 * h + 8 * s);
-                    const rh8 bl = *reinterpret_cast<const rh8*>(bq + ((qt * 2 + 1) * 32 + i) * RS_BROW + 64 * h + 8 * s);
-                    acch = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh, acch, 0, 0, 0);
-                    accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl, accl, 0, 0, 0);
-                    if constexpr (L::LO) accm = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh, accm, 0, 0, 0);
-                }
-                float mx = FLMR_NEG_INF;
-                int arg = 0x7fffffff;   // the lowest row holding mx (rows ascend with r for a fixed h)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    // fp16 store: accm is the +0 the fp32 kernel accumulates from all-zero low parts
-                    const float v = ((okbits >> r) & 1u) ? fmaf(accl[r] + accm[r], 1.0f / 2048.0f, acch[r]) : -9999.0f;  // colbert.py:240
-                    if (row < Ld && v > mx) { mx = v; arg = row; }
-                }
-                const int col = qc0 + qt * 32 + i;
-                const float omx = __shfl_xor(mx, 32, 64);
-                const int oarg = __shfl_xor(arg, 32, 64);
-                if (omx > mx || (omx == mx && oarg < arg)) { mx = omx; arg = oarg; }
-                if (h == 0 && col < nq && mx > FLMR_NEG_INF)
-                    atomicMax(&colkey[col], ((unsigned long long)flmr_f2ord(mx) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)arg));
+                mt_products<true, L::LO>(bq, qt, i, h, ah, al, acch, accl, accm);   // fp16 store: no lo(D) x hi(Q)
+                mt_fold<true>(acch, accl, accm, okbits, t, h, Ld, qc0 + qt * 32 + i, nq, colkey);
             }
         }
     }
     __syncthreads();
-    auto cmax = [&](int c) -> float { return doc.cols ? flmr_ord2f((unsigned int)(colkey[c] >> 32)) : FLMR_NEG_INF; };
-    for (int c = tid; c < nq; c += 256) {
-        const int tok = doc.cols ? (int)(0xFFFFFFFFu - (uint32_t)colkey[c]) : -1;
-        argmax_out[ob * nq + c] = (live && tok >= 0 && ld.ok(doc, tok)) ? tok : -1;
-    }
-    if (colmax_out)
-        for (int c = tid; c < nq; c += 256) colmax_out[ob * nq + c] = cmax(c);
-    if (tid == 0 && out) {
-        float sc = 0.0f;
-        for (int c = 0; c < nq; c++) sc += cmax(c);
-        out[ob] = sc;
-    }
+    mt_epilogue<true>(colkey, doc.cols, [=](int tok) { return live && ld.ok(doc, tok); }, ob, nq, tid, out, colmax_out, argmax_out);
 }
 
 // one wave per (query q, column i); lane l owns dims 2l, 2l+1; the k rows of the query 64 at a time, added in ascending j
@@ -360,9 +286,8 @@ __global__ __launch_bounds__(256) void maxsim_gather_grad_q_kernel(const L ld,
 
 static int gather_sizes(int32_t store_dtype, int32_t npassages, int32_t Ld, int32_t dim, int32_t nqueries, int32_t k, int32_t nq) {
     if (store_dtype != FLMR_F32 && store_dtype != FLMR_F16) FLMR_FAIL(FLMR_ERR_INVALID, "store_dtype=%d (FLMR_F32 or FLMR_F16)", store_dtype);
-    if (nq < 1 || nqueries < 0 || k < 0 || npassages < 0 || Ld < 0) FLMR_FAIL(FLMR_ERR_INVALID, "bad sizes");
-    if (dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dim=%d (this build: %d)", dim, FLMR_DIM);
-    if ((size_t)nq * 8 > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
+    const int rc = flmr_maxsim_check(1, 1, 0, nq >= 1 && nqueries >= 0 && k >= 0 && npassages >= 0 && Ld >= 0, 0, dim, nq, FLMR_MAXSIM_NQ_KEYS);
+    if (rc) return rc;
     if ((int64_t)nqueries * k > 0x7fffffffll) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nqueries * k = %lld rows", (long long)nqueries * k);
     return FLMR_OK;
 }
@@ -371,7 +296,7 @@ template <class L>
 static int launch_fwd(const L& ld, const float* Q, int32_t nqueries, int32_t nq, const int32_t* pids, int32_t k, float* out, float* colmax,
                       int32_t* argmax, hipStream_t st) {
     const int nqp = (int)((nq + 31) / 32 * 32);
-    const size_t lds = (size_t)RS_QC * 2 * 32 * RS_BROW * sizeof(_Float16) + (size_t)nqp * sizeof(unsigned long long) + L::lds_bytes();
+    const size_t lds = mt_stage_bytes<2>() + (size_t)nqp * sizeof(unsigned long long) + L::lds_bytes();
     const dim3 grid((unsigned)((int64_t)nqueries * k));
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(maxsim_gather_fwd_kernel<L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(maxsim_gather_fwd_kernel<L>, grid, dim3(256), lds, st, Q, (int)nq, nqp, ld, pids, (int)k, out, colmax, argmax);
@@ -397,7 +322,8 @@ extern "C" int flmr_maxsim_gather_fwd(const float* Q, int32_t nqueries, int32_t 
     if ((int64_t)nqueries * k == 0) return FLMR_OK;
     if (!Q || !pids || !argmax) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
     if ((int64_t)npassages * Ld > 0 && (!store || !store_mask)) FLMR_FAIL(FLMR_ERR_INVALID, "NULL store");
-    if ((reinterpret_cast<uintptr_t>(store) | reinterpret_cast<uintptr_t>(Q)) & 15) FLMR_FAIL(FLMR_ERR_INVALID, "Q and store must be 16-byte aligned");
+    const int ra = flmr_maxsim_check(1, 1, 0, true, reinterpret_cast<uintptr_t>(store) | reinterpret_cast<uintptr_t>(Q), FLMR_DIM, nq, FLMR_MAXSIM_NQ_ANY);
+    if (ra) return ra;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (store_dtype == FLMR_F16)
         return launch_fwd(rs_store_loader<true>{store, store_mask, (int)npassages, (int)Ld}, Q, nqueries, nq, pids, k, out, colmax, argmax, st);
@@ -421,10 +347,9 @@ extern "C" int flmr_maxsim_gather_bwd(const void* store, int32_t store_dtype, in
 // ---- the compressed index as the store ------------------------------------------------------------------------------
 static int index_sizes(const flmr_index* ix, int32_t nqueries, int32_t k, int32_t nq) {
     if (!ix) FLMR_FAIL(FLMR_ERR_INVALID, "NULL index");
-    if (nq < 1 || nqueries < 0 || k < 0) FLMR_FAIL(FLMR_ERR_INVALID, "bad sizes");
-    if (ix->dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dim=%d (this build: %d)", ix->dim, FLMR_DIM);
+    const int rc = flmr_maxsim_check(1, 1, 0, nq >= 1 && nqueries >= 0 && k >= 0, 0, ix->dim, nq, FLMR_MAXSIM_NQ_KEYS);
+    if (rc) return rc;
     if (ix->nbits != 1 && ix->nbits != 2 && ix->nbits != 4 && ix->nbits != 8) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nbits=%d", ix->nbits);
-    if ((size_t)nq * 8 > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
     if ((int64_t)nqueries * k > 0x7fffffffll) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nqueries * k = %lld rows", (long long)nqueries * k);
     return FLMR_OK;
 }
@@ -447,7 +372,8 @@ extern "C" int flmr_maxsim_index_fwd(const flmr_index_t* ix, const float* Q, int
     if (rc) return rc;
     if ((int64_t)nqueries * k == 0) return FLMR_OK;
     if (!Q || !pids || !argmax) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(Q) & 15) FLMR_FAIL(FLMR_ERR_INVALID, "Q must be 16-byte aligned");
+    const int ra = flmr_maxsim_check(1, 1, 0, true, reinterpret_cast<uintptr_t>(Q), FLMR_DIM, nq, FLMR_MAXSIM_NQ_ANY);
+    if (ra) return ra;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #define RS_FWD(ld) [&](const auto& l) { return launch_fwd(l, Q, nqueries, nq, pids, k, out, colmax, argmax, st); }(ld)
     RS_NB(RS_FWD)

@@ -145,10 +145,8 @@ static int maxsim_bwd(const void* Q, int32_t q_dtype, int32_t q_batch, int32_t n
                       int32_t dim, int32_t cross, const int32_t* argmax, const float* grad_colmax, void* dQ, int32_t dq_dtype, void* dD,
                       int32_t dd_dtype, flmr_stream_t stream) {
     if (!Q || !D || !argmax || !grad_colmax) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
-    if (!cross && q_batch != 1 && q_batch != B) FLMR_FAIL(FLMR_ERR_INVALID, "q_batch must be 1 or B");
-    if (cross && (q_batch < 1 || q_batch > 65535)) FLMR_FAIL(FLMR_ERR_INVALID, "cross scoring takes 1..65535 queries per call");
-    if (nq < 1 || B < 0 || Ld < 0) FLMR_FAIL(FLMR_ERR_INVALID, "bad sizes");
-    if (dim != FLMR_DIM) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dim=%d (this build: %d)", dim, FLMR_DIM);
+    const int rc = flmr_maxsim_check(q_batch, B, cross, nq >= 1 && B >= 0 && Ld >= 0, 0, dim, nq, FLMR_MAXSIM_NQ_ANY);   // (no column state in LDS)
+    if (rc) return rc;
     if (B > 65535 && dD) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "B=%d > 65535", B);
     if (B == 0) return FLMR_OK;
     if (cross && q_batch == 1) cross = 0;   // (the broadcast form: the same rows, the same sums)
@@ -177,9 +175,11 @@ extern "C" int flmr_colbert_maxsim_bwd_typed(const void* Q, int32_t q_dtype, int
     const int32_t dts[4] = {q_dtype, d_dtype, dq_dtype, dd_dtype};
     for (int k = 0; k < 4; k++)
         if (dts[k] != FLMR_F32 && dts[k] != FLMR_F16) FLMR_FAIL(FLMR_ERR_INVALID, "dtype=%d (FLMR_F32 or FLMR_F16)", dts[k]);
-    if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dD)) & 15)
-        FLMR_FAIL(FLMR_ERR_INVALID, "Q, D, dQ and dD must be 16-byte aligned");
-    if ((size_t)(nq > 0 ? nq : 0) * 8 > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large", nq);
+    // the typed ABI's own rules, ahead of the rest: alignment, and the forward's nq limit (nq < 1 is "bad sizes" below)
+    const int rc = flmr_maxsim_check(1, 1, 0, true,
+                                     reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dD),
+                                     FLMR_DIM, nq > 0 ? nq : 0, FLMR_MAXSIM_NQ_KEYS);
+    if (rc) return rc;
     if (q_dtype == FLMR_F16 && d_dtype == FLMR_F32 && dim == FLMR_DIM)
         FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "fp16 Q with fp32 D: widen Q and call the fp32 entry point");
     return maxsim_bwd(Q, q_dtype, q_batch, nq, D, d_dtype, B, Ld, dim, cross, argmax, grad_colmax, dQ, dq_dtype, dD, dd_dtype, stream);

@@ -170,6 +170,18 @@ def colbert_colmax_padded(Q, D_padded, D_mask):
     return out
 
 
+def _maxsim_fwd_outputs(lead, nq, want_out, want_colmax, empty, launch):
+    """The outputs of a MaxSim forward: allocates (out f32 [*lead] | None, colmax f32 [*lead, nq] | None, argmax i32 [*lead, nq])
+    and has launch(out, colmax, argmax) fill them, unless the batch is `empty` (empty tensors may have NULL data pointers, which
+    the C ABI rejects)."""
+    out = torch.empty(lead, dtype=torch.float32, device="cuda") if want_out else None
+    colmax = torch.empty(lead + (nq,), dtype=torch.float32, device="cuda") if want_colmax else None
+    argmax = torch.empty(lead + (nq,), dtype=torch.int32, device="cuda")
+    if not empty:
+        launch(out, colmax, argmax)
+    return out, colmax, argmax
+
+
 def colbert_maxsim_fwd(Q, D_padded, D_mask, cross=False, want_out=True, want_colmax=False):
     """The autograd forward (flmr_colbert_maxsim_fwd / _fwd_typed): CUDA Q [q_batch, Nq, 128], D [B, Ld, 128], mask [B, Ld(,1)] ->
     (out f32 [rows] | None, colmax f32 [rows, Nq] | None, argmax i32 [rows, Nq]); rows = B, or q_batch * B query-major when
@@ -183,19 +195,15 @@ def colbert_maxsim_fwd(Q, D_padded, D_mask, cross=False, want_out=True, want_col
     B, Ld, dim = Dd.shape
     nQ, nq = Qd.size(0), Qd.size(1)
     md = _d(torch.as_tensor(D_mask).reshape(B, Ld), torch.bool).view(torch.uint8)
-    lead = (nQ, B) if cross else (B,)
-    out = torch.empty(lead, dtype=torch.float32, device="cuda") if want_out else None
-    colmax = torch.empty(lead + (nq,), dtype=torch.float32, device="cuda") if want_colmax else None
-    argmax = torch.empty(lead + (nq,), dtype=torch.int32, device="cuda")
-    if B == 0:
-        return out, colmax, argmax   # (empty tensors may have NULL data pointers, which the C ABI rejects)
-    if typed:
-        _native.check(lib.flmr_colbert_maxsim_fwd_typed(_p(Qd), _ft(Qd.dtype), nQ, nq, _p(Dd), _ft(Dd.dtype), _p(md), B, Ld, dim,
-                                                        int(bool(cross)), _p(out), _p(colmax), _p(argmax), _native.stream_ptr()))
-        return out, colmax, argmax
-    _native.check(lib.flmr_colbert_maxsim_fwd(_p(Qd), nQ, nq, _p(Dd), _p(md), B, Ld, dim, int(bool(cross)), _p(out), _p(colmax),
-                                              _p(argmax), _native.stream_ptr()))
-    return out, colmax, argmax
+
+    def launch(out, colmax, argmax):
+        if typed:
+            _native.check(lib.flmr_colbert_maxsim_fwd_typed(_p(Qd), _ft(Qd.dtype), nQ, nq, _p(Dd), _ft(Dd.dtype), _p(md), B, Ld, dim,
+                                                            int(bool(cross)), _p(out), _p(colmax), _p(argmax), _native.stream_ptr()))
+        else:
+            _native.check(lib.flmr_colbert_maxsim_fwd(_p(Qd), nQ, nq, _p(Dd), _p(md), B, Ld, dim, int(bool(cross)), _p(out), _p(colmax),
+                                                      _p(argmax), _native.stream_ptr()))
+    return _maxsim_fwd_outputs((nQ, B) if cross else (B,), nq, want_out, want_colmax, B == 0, launch)
 
 
 def colbert_maxsim_bwd(Q, D_padded, argmax, grad_colmax, cross=False, need_dQ=True, need_dD=True, dq_dtype=torch.float32,
@@ -252,14 +260,11 @@ def maxsim_gather_fwd(Q, store, store_mask, pids, want_out=True, want_colmax=Fal
     n, nq = Qd.size(0), Qd.size(1)
     assert pd.dim() == 2 and pd.size(0) == n, (tuple(pd.shape), n)
     k = pd.size(1)
-    out = torch.empty((n, k), dtype=torch.float32, device="cuda") if want_out else None
-    colmax = torch.empty((n, k, nq), dtype=torch.float32, device="cuda") if want_colmax else None
-    argmax = torch.empty((n, k, nq), dtype=torch.int32, device="cuda")
-    if n * k == 0:
-        return out, colmax, argmax   # (empty tensors may have NULL data pointers, which the C ABI rejects)
-    _native.check(lib.flmr_maxsim_gather_fwd(_p(Qd), n, nq, _p(sd), _store_dtype(sd), _p(md), P, Ld, dim, _p(pd), k, _p(out),
-                                             _p(colmax), _p(argmax), _native.stream_ptr()))
-    return out, colmax, argmax
+
+    def launch(out, colmax, argmax):
+        _native.check(lib.flmr_maxsim_gather_fwd(_p(Qd), n, nq, _p(sd), _store_dtype(sd), _p(md), P, Ld, dim, _p(pd), k, _p(out),
+                                                 _p(colmax), _p(argmax), _native.stream_ptr()))
+    return _maxsim_fwd_outputs((n, k), nq, want_out, want_colmax, n * k == 0, launch)
 
 
 def maxsim_gather_bwd(store, pids, argmax, grad_colmax):
@@ -291,16 +296,13 @@ def maxsim_index_fwd(device_index, Q, pids, want_out=True, want_colmax=False):
     n, nq = Qd.size(0), Qd.size(1)
     assert Qd.dim() == 3 and pd.dim() == 2 and pd.size(0) == n, (tuple(Qd.shape), tuple(pd.shape))
     k = pd.size(1)
-    out = torch.empty((n, k), dtype=torch.float32, device="cuda") if want_out else None
-    colmax = torch.empty((n, k, nq), dtype=torch.float32, device="cuda") if want_colmax else None
-    argmax = torch.empty((n, k, nq), dtype=torch.int32, device="cuda")
-    if n * k == 0:
-        return out, colmax, argmax   # (empty tensors may have NULL data pointers, which the C ABI rejects)
-    if Qd.size(2) != device_index.arrays.dim:
-        raise ValueError(f"Q has dim {Qd.size(2)}, the index {device_index.arrays.dim}")
-    _native.check(lib.flmr_maxsim_index_fwd(device_index.handle, _p(Qd), n, nq, _p(pd), k, _p(out), _p(colmax), _p(argmax),
-                                            _native.stream_ptr()))
-    return out, colmax, argmax
+
+    def launch(out, colmax, argmax):
+        if Qd.size(2) != device_index.arrays.dim:
+            raise ValueError(f"Q has dim {Qd.size(2)}, the index {device_index.arrays.dim}")
+        _native.check(lib.flmr_maxsim_index_fwd(device_index.handle, _p(Qd), n, nq, _p(pd), k, _p(out), _p(colmax), _p(argmax),
+                                                _native.stream_ptr()))
+    return _maxsim_fwd_outputs((n, k), nq, want_out, want_colmax, n * k == 0, launch)
 
 
 def maxsim_index_bwd(device_index, pids, argmax, grad_colmax):

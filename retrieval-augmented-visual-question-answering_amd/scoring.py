@@ -64,6 +64,20 @@ def colbert_score(Q, D_padded, D_mask, config=None, use_gpu=False):
 _device = "cuda"   # where the kernels run (the CPU plumbing tests point this at "cpu" with stand-in ops)
 
 
+def _grad_colmax(grad, argmax, want_colmax):
+    """dL/dcolmax, fp32 and contiguous, shaped like argmax, from the gradient of what a MaxSim Function returned: the column
+    maxima themselves, or their sum (every column of a row then shares the row's gradient)."""
+    return (grad.float() if want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)).contiguous()
+
+
+def _reduced(apply, config, shape):
+    """The scores, shaped `shape`, of a MaxSim Function called as apply(want_colmax): its own row sums for 'colbert', its
+    differentiable column maxima reduced by reduce_colmax for 'flipr'."""
+    if _interaction(config) == "flipr":
+        return reduce_colmax(apply(True).flatten(0, -2), config).reshape(shape)
+    return apply(False)
+
+
 class _MaxSim(torch.autograd.Function):
     """Padded MaxSim with the gradient torch's autograd gives colbert_score_reduce (colbert.py:235-263): each column's
     gradient goes to its winning token, the lowest one on ties, and nowhere when that token is padded.  Returns the kernel's
@@ -94,13 +108,13 @@ class _MaxSim(torch.autograd.Function):
         need_dQ, need_dD = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_dQ or need_dD):
             return None, None, None, None, None
-        G = grad.float() if ctx.want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)
+        G = _grad_colmax(grad, argmax, ctx.want_colmax)
         Qk, Dk, native = _MaxSim._operands(Q, D_padded)
         if native and (Q.dtype, D_padded.dtype) != (torch.float32, torch.float32):   # the kernels write each input's dtype
-            dQ, dD = ops.colbert_maxsim_bwd(Qk, Dk, argmax, G.contiguous(), cross=ctx.cross, need_dQ=need_dQ, need_dD=need_dD,
+            dQ, dD = ops.colbert_maxsim_bwd(Qk, Dk, argmax, G, cross=ctx.cross, need_dQ=need_dQ, need_dD=need_dD,
                                             dq_dtype=Q.dtype, dd_dtype=D_padded.dtype)
             return dQ, dD, None, None, None
-        dQ, dD = ops.colbert_maxsim_bwd(Qk, Dk, argmax, G.contiguous(), cross=ctx.cross, need_dQ=need_dQ, need_dD=need_dD)
+        dQ, dD = ops.colbert_maxsim_bwd(Qk, Dk, argmax, G, cross=ctx.cross, need_dQ=need_dQ, need_dD=need_dD)
         return (dQ.to(Q.dtype) if need_dQ else None, dD.to(D_padded.dtype) if need_dD else None, None, None, None)
 
 
@@ -110,33 +124,49 @@ def _maxsim(Q, D_padded, D_mask, config, cross):
     if not cross and Q.size(0) not in (1, D_padded.size(0)):
         raise ValueError(f"Q.size(0) = {Q.size(0)} must be 1 or B = {D_padded.size(0)}")   # colbert.py:278
     Q, D_padded = Q.to(_device), D_padded.to(_device)
-    if _interaction(config) == "flipr":
-        return reduce_colmax(_MaxSim.apply(Q, D_padded, D_mask, cross, True).flatten(0, -2), config).reshape(
-            (Q.size(0), D_padded.size(0)) if cross else (D_padded.size(0),))
-    return _MaxSim.apply(Q, D_padded, D_mask, cross, False)
+    return _reduced(lambda want_colmax: _MaxSim.apply(Q, D_padded, D_mask, cross, want_colmax), config,
+                    (Q.size(0), D_padded.size(0)) if cross else (D_padded.size(0),))
 
 
-class _MaxSimGather(torch.autograd.Function):
-    """_MaxSim whose documents are rows of a resident passage store picked by pid: row (q, j) is query q against passage
-    pids[q, j] (< 0: an empty slot, an all-padded document).  Saves (Q, pids, argmax) and the store by reference; the store is a
-    constant of training, so Q is the only input with a gradient.  Returns [n, k] sums or [n, k, Nq] column maxima."""
+# A document source of _MaxSimGathered: (fwd(Q, pids, want_out=, want_colmax=), bwd(pids, argmax, G), tensors) -- the `ops` calls
+# that read it (`ops` is looked up at each call: the CPU plumbing tests swap it) and the tensors it is made of, which the
+# Function takes as inputs without a gradient.
+def _store_source(store, store_mask):
+    """The rows of a resident passage store [P, Ld, 128] (fp32 / fp16) + mask [P, Ld]."""
+    return (lambda Q, pids, **want: ops.maxsim_gather_fwd(Q, store, store_mask, pids, **want),
+            lambda pids, argmax, G: ops.maxsim_gather_bwd(store, pids, argmax, G), (store, store_mask))
+
+
+def _index_source(device_index):
+    """The resident compressed index (index.DeviceIndex): the passages' tokens are decompressed and normalised in the kernels."""
+    return (lambda Q, pids, **want: ops.maxsim_index_fwd(device_index, Q, pids, **want),
+            lambda pids, argmax, G: ops.maxsim_index_bwd(device_index, pids, argmax, G), ())
+
+
+class _MaxSimGathered(torch.autograd.Function):
+    """_MaxSim whose documents are passages of a document source picked by pid: row (q, j) is query q against passage
+    pids[q, j] (< 0: an empty slot, an all-padded document).  Saves (Q, pids, argmax) and the source by reference; the source is
+    a constant of training, so Q is the only input with a gradient.  Returns [n, k] sums or [n, k, Nq] column maxima."""
 
     @staticmethod
-    def forward(ctx, Q, store, store_mask, pids, want_colmax):
-        out, colmax, argmax = ops.maxsim_gather_fwd(Q.detach().float(), store, store_mask, pids, want_out=not want_colmax,
-                                                    want_colmax=want_colmax)
-        ctx.save_for_backward(Q, store, pids, argmax)
-        ctx.want_colmax = want_colmax
+    def forward(ctx, Q, source, pids, want_colmax, *source_tensors):
+        out, colmax, argmax = source[0](Q.detach().float(), pids, want_out=not want_colmax, want_colmax=want_colmax)
+        ctx.save_for_backward(Q, pids, argmax)
+        ctx.source, ctx.want_colmax = source, want_colmax
         return colmax if want_colmax else out
 
     @staticmethod
     def backward(ctx, grad):
-        Q, store, pids, argmax = ctx.saved_tensors
+        Q, pids, argmax = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
-        G = grad.float() if ctx.want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)
-        dQ = ops.maxsim_gather_bwd(store, pids, argmax, G.contiguous())
-        return dQ.to(Q.dtype), None, None, None, None
+            return (None,) * len(ctx.needs_input_grad)
+        dQ = ctx.source[1](pids, argmax, _grad_colmax(grad, argmax, ctx.want_colmax))
+        return (dQ.to(Q.dtype),) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+def _gathered(Q, source, pids, config):
+    Q, pids = Q.to(_device), pids.to(device=_device, dtype=torch.int32)
+    return _reduced(lambda want_colmax: _MaxSimGathered.apply(Q, source, pids, want_colmax, *source[2]), config, pids.shape)
 
 
 def maxsim_gather_differentiable(Q, store, store_mask, pids, config=None):
@@ -149,34 +179,7 @@ def maxsim_gather_differentiable(Q, store, store_mask, pids, config=None):
                          "[P, Ld, d] and [n, k]")
     if store.requires_grad:
         raise RuntimeError("the passage store is a constant of training: there is no store gradient (detach it)")
-    Q, pids = Q.to(_device), pids.to(device=_device, dtype=torch.int32)
-    if _interaction(config) == "flipr":
-        colmax = _MaxSimGather.apply(Q, store, store_mask, pids, True)
-        return reduce_colmax(colmax.flatten(0, 1), config).reshape(pids.shape)
-    return _MaxSimGather.apply(Q, store, store_mask, pids, False)
-
-
-class _MaxSimIndex(torch.autograd.Function):
-    """_MaxSimGather whose passage store is the resident compressed index (index.DeviceIndex): the tokens of passage pids[q, j]
-    are decompressed and normalised inside the kernels.  Saves (Q, pids, argmax) and the index by reference; the index is a
-    constant, so Q is the only input with a gradient.  Returns [n, k] sums or [n, k, Nq] column maxima."""
-
-    @staticmethod
-    def forward(ctx, Q, device_index, pids, want_colmax):
-        out, colmax, argmax = ops.maxsim_index_fwd(device_index, Q.detach().float(), pids, want_out=not want_colmax,
-                                                   want_colmax=want_colmax)
-        ctx.save_for_backward(Q, pids, argmax)
-        ctx.device_index, ctx.want_colmax = device_index, want_colmax
-        return colmax if want_colmax else out
-
-    @staticmethod
-    def backward(ctx, grad):
-        Q, pids, argmax = ctx.saved_tensors
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        G = grad.float() if ctx.want_colmax else grad.float().unsqueeze(-1).expand(argmax.shape)
-        dQ = ops.maxsim_index_bwd(ctx.device_index, pids, argmax, G.contiguous())
-        return dQ.to(Q.dtype), None, None, None
+    return _gathered(Q, _store_source(store, store_mask), pids, config)
 
 
 def maxsim_index_differentiable(Q, device_index, pids, config=None):
@@ -187,11 +190,7 @@ def maxsim_index_differentiable(Q, device_index, pids, config=None):
     index and a passage of length 0 score as all-padded documents."""
     if Q.dim() != 3 or pids.dim() != 2 or pids.size(0) != Q.size(0):
         raise ValueError(f"Q {tuple(Q.shape)} / pids {tuple(pids.shape)}: expected [n, Nq, d] and [n, k]")
-    Q, pids = Q.to(_device), pids.to(device=_device, dtype=torch.int32)
-    if _interaction(config) == "flipr":
-        colmax = _MaxSimIndex.apply(Q, device_index, pids, True)
-        return reduce_colmax(colmax.flatten(0, 1), config).reshape(pids.shape)
-    return _MaxSimIndex.apply(Q, device_index, pids, False)
+    return _gathered(Q, _index_source(device_index), pids, config)
 
 
 def colbert_score_differentiable(Q, D_padded, D_mask, config=None):
