@@ -47,7 +47,7 @@ int main() {
     for (int c : surv) bits[c >> 5] |= 1u << (c & 31);
     { uint32_t run = 0; for (int w = 0; w < idx_words; w++) { prefix[w] = run; run += __builtin_popcount(bits[w]); } }
     // passages: distinct ascending codes first, the rest of the 128-token run repeats the last
-    std::vector<int32_t> codes((size_t)P * L + 256, 0x7f7f7f7f);
+    std::vector<int32_t> codes((size_t)P * L + FLMR_CODE_PAD, 0);   // (the pad as flmr_build_sorted_codes leaves it: code 0)
     std::vector<uint16_t> ulen(P);
     std::vector<int64_t> off(P + 1);
     for (int p = 0; p <= P; p++) off[p] = (int64_t)p * L;

@@ -12,7 +12,12 @@
 #define FLMR_MAX_NCELLS 8
 #define FLMR_MAX_NQ_CAND 128    // candidate-generation width limit (4 column tiles of 32)
 #define FLMR_MAX_NDOCS 8192
-#define FLMR_CODE_PAD 256        // ints readable behind the sorted code copy (the dense stage 1 reads whole 16-byte pieces)
+#define FLMR_SORTED_MAX_DOCLEN 2048   // longest passage of an index that gets a sorted code copy (sort_doc_codes_kernel sorts a passage in LDS)
+// ints readable behind the sorted code copy, all of them code 0.  The dense stage 1 requests a later chunk of a round's codes for
+// EVERY candidate of the round once one of them has that many: a 1-token passage that closes the index, in a round with a passage
+// of FLMR_SORTED_MAX_DOCLEN codes, is read less than FLMR_SORTED_MAX_DOCLEN + 256 (the largest chunk) ints behind its start
+// (flmr_stage1_dense.hip derives the bound next to its static_assert); the stage-2 walk reads 8 ints behind a run
+#define FLMR_CODE_PAD (FLMR_SORTED_MAX_DOCLEN + 256)
 
 extern thread_local char flmr_err_buf[512];
 
@@ -139,7 +144,8 @@ struct flmr_index {
     uint32_t* ivf_chunk_tab;      // [K][nchunks+1]: first entry of each IVF list with pid >= chunk*32768
     int32_t nchunks;
     int32_t* codes_sorted;        // [N + FLMR_CODE_PAD] per-passage ascending copy of `codes` with the DISTINCT values first (the rest of a
-                                  // passage's run repeats its largest code: still ascending, the same set); NULL when a passage is too long
+                                  // passage's run repeats its largest code: still ascending, the same set), the pad filled with code 0; NULL when a passage
+                                  // is longer than FLMR_SORTED_MAX_DOCLEN
     uint16_t* doc_ulen;           // [num_passages] distinct codes per passage = the length of the distinct prefix in codes_sorted; NULL when
                                   // fewer than a tenth of the tokens repeat a code of their passage (every token then counts)
     double dup_share;             // share of the tokens that repeat a code of their passage (0 when codes_sorted was not built)
@@ -380,7 +386,7 @@ int flmr_launch_maxsim(const flmr_maxsim_args& a, s3_form form, hipStream_t st);
 
 // ---- stage 1 for dense survivor sets (flmr_stage1_dense.hip) ----
 struct flmr_s1d_args {
-    const int32_t* codes;        // `codes_sorted`: per-passage runs, distinct values first, FLMR_CODE_PAD ints readable behind the last
+    const int32_t* codes;        // `codes_sorted`: per-passage runs, distinct values first, FLMR_CODE_PAD ints of code 0 behind the last
     const int64_t* offsets;      // [num_passages + 1]
     const uint16_t* ulen;        // [num_passages] distinct codes per passage (NULL: every token, offsets[p+1] - offsets[p])
     const uint32_t* idx_bits;    // [nqueries, idx_words] surviving-centroid mask (index_storage.py:116)
@@ -401,7 +407,7 @@ struct flmr_s1d_args {
     float* img_err;              // [nqueries] out (IMG pass): E + eps of the band rule (inf: the images cannot be used)
     int32_t parts;               // items per query (0: the launcher's choice)
     int32_t group;               // candidates per wave and group: 64, or 16 for short lists
-    int64_t codes_len;           // tokens at `codes`; FLMR_CODE_PAD more ints must be readable behind them
+    int64_t codes_len;           // tokens at `codes`; FLMR_CODE_PAD more ints, each a valid code, must be readable behind them (every chunk of a round)
     int32_t img_rows;            // rows of images the launch's LDS holds (IMG pass; set by the launcher)
     const int32_t* any;          // nullable: [0] some query takes the IMG pass, [1] some query takes the EXACT pass (flmr_launch_s1_dense_modes)
 };

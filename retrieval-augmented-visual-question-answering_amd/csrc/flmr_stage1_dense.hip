@@ -47,7 +47,13 @@
 #define D1_LOAD(p) (*(p))
 #endif
 #define D1_THREADS (64 * D1_WAVES)
-#define D1_CODE_PAD FLMR_CODE_PAD   // ints readable beyond the last passage's codes (flmr_build_sorted_codes pads the copy)
+#define D1_MAX_LISTCAP 256   // the largest LPC x CPL instantiated below (32 x 8): codes of one candidate chunk
+// The furthest word either kernel requests for a candidate whose run starts at `off`: a later chunk is requested for EVERY candidate of
+// a round while ANY of them has more than t0 + LISTCAP codes (a wave-uniform ballot), at off + t0 + LISTCAP + CPL * l + [0, CPL), so
+// at most off + t0 + 2 LISTCAP - 1 with t0 + LISTCAP below the round's longest run (<= FLMR_SORTED_MAX_DOCLEN).  The candidate may be
+// a 1-token passage that closes the index: flmr_build_sorted_codes keeps FLMR_CODE_PAD ints of code 0 behind the last token.
+static_assert(FLMR_CODE_PAD >= FLMR_SORTED_MAX_DOCLEN + D1_MAX_LISTCAP - 1,
+              "the sorted copy's pad must cover a later chunk requested for the index's last passage");
 #define D1_XCDS 8
 
 typedef uint32_t d1u4 __attribute__((ext_vector_type(4)));
@@ -128,6 +134,7 @@ template <int LPC, int CPL>
 __global__ __launch_bounds__(D1_THREADS) void s1_image_kernel(flmr_s1d_args a) {
     constexpr int R = 64 / LPC;            // candidates per round
     constexpr int LISTCAP = LPC * CPL;     // codes (= most hits) of one candidate chunk
+    static_assert(LISTCAP <= D1_MAX_LISTCAP, "FLMR_CODE_PAD is sized for chunks of at most D1_MAX_LISTCAP codes");
     constexpr int NV = CPL / 4;            // 16-byte requests per lane and round
     constexpr int LPR = 4;                 // lanes per image row (16 bytes = 8 fp16 columns each)
     constexpr int HPI = LPC / LPR;         // hits folded per iteration and candidate
@@ -266,7 +273,7 @@ __global__ __launch_bounds__(D1_THREADS) void s1_image_kernel(flmr_s1d_args a) {
             float ukeep = 0.0f;   // lane j: the score of candidate j of the group
             // Codes of round r (first chunk): CPL codes of this lane's candidate, requested TWO ROUNDS AHEAD and ALWAYS (past the
             // group's end some candidate's codes are read again): what a lane reads beyond its passage's end -- the next passage's
-            // codes, the sorted copy's FLMR_CODE_PAD words of padding -- is masked by the listing
+            // codes, the sorted copy's FLMR_CODE_PAD words of padding (code 0: FLMR_CODE_PAD covers every chunk) -- is masked by the listing
             auto request_codes = [&](d1i4u (&c_)[NV], int r, int t0, int& jlen) {
                 const int j = r * R + sub;
                 const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute(j << 2, (int)off);
@@ -450,6 +457,7 @@ template <int LPC, int CPL>
 __global__ __launch_bounds__(D1_THREADS) void s1_exact_kernel(flmr_s1d_args a) {
     constexpr int R = 64 / LPC;            // candidates per round
     constexpr int LISTCAP = LPC * CPL;     // codes (= most hits) of one candidate chunk
+    static_assert(LISTCAP <= D1_MAX_LISTCAP, "FLMR_CODE_PAD is sized for chunks of at most D1_MAX_LISTCAP codes");
     constexpr int NV = CPL / 4;            // 16-byte requests per lane and round
     constexpr int LPR = 8;                 // lanes per fp32 row (16 bytes each)
     constexpr int HPI = LPC / LPR;         // hits folded per iteration and candidate

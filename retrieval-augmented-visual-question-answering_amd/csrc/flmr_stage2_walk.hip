@@ -70,7 +70,7 @@ __device__ __forceinline__ float w2_dec(int e) { return __int_as_float(e ^ ((e >
 #define W2_DOCS (W2_WAVES * 128)     // passages per work item: two per lane
 #define W2_BUF ((W2_SLICE + 1) * W2_STRIDE)   // words per buffer: the score rows + one dummy row (the smallest image)
 #define W2_INF 0x7fffffff
-#define W2_MAX_DOCLEN 2048           // longest passage the in-LDS code sort handles
+#define W2_MAX_DOCLEN FLMR_SORTED_MAX_DOCLEN   // longest passage the in-LDS code sort handles
 
 // ------------------------------------------------------------------------------------------------
 // codes_sorted[off[p] .. off[p+1]) = ascending copy of codes[off[p] .. off[p+1]) with the DISTINCT values first: the first
@@ -183,7 +183,7 @@ int flmr_build_sorted_codes(flmr_index* ix) {
         ix->codes_sorted = nullptr; ix->doc_ulen = nullptr;
         return FLMR_OK;
     }
-    FLMR_HIP(hipMemset(ix->codes_sorted + ix->N, 0x7f, FLMR_CODE_PAD * sizeof(int32_t)));
+    FLMR_HIP(hipMemset(ix->codes_sorted + ix->N, 0, FLMR_CODE_PAD * sizeof(int32_t)));   // code 0: the dense stage 1 probes its mask with every word it reads
     FLMR_HIP(hipMemset(d_total, 0, sizeof(unsigned long long)));
     const int64_t grid = ix->num_passages < 262144 ? ix->num_passages : 262144;
     hipLaunchKernelGGL(sort_doc_codes_kernel, dim3((unsigned)grid), dim3(64), 0, 0, ix->codes, ix->doc_offsets, ix->num_passages,
