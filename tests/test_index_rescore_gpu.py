@@ -4,7 +4,8 @@ Searcher.retrieve_and_rescore(Q, None, ...)):
 * seeded shapes on an index built on the device -- doclens at the tile edge (31, 32, 33), at the four-wave wrap of the tile
   loop (127, 128, 129), 1, 300 and the FLMR maximum 512; Nq 32 and 320 (three passes of 128 staged columns) -- against the
   float64 restatement (tests/index_rescore_common.py, pinned by tests/test_index_rescore_host.py), with the share of near-tie
-  columns the winner comparison leaves out bounded; dQ against float64 from the kernel's own argmax;
+  columns the winner comparison leaves out bounded; dQ against float64 from the kernel's own argmax; k = 65 and 130 passages per
+  query (further trips of the dQ wave's walk over a query's rows, 64 at a time);
 * against the search's own scores; end to end against an fp32 PassageEmbeddingStore filled from the index;
 * an index whose centroids are not fp16-representable; determinism, a non-default stream, half queries, 'flipr', the C ABI's
   error codes, pid validation; the memory bound at the RAG training shape."""
@@ -148,6 +149,43 @@ def test_seeded_shapes_against_float64(hip, built, nbits, Nq):
     assert arrays.doclens[:10].tolist() == EDGE_DOCLENS + [0]
     Q, pids = seeded_case(hip.torch, rows, arrays.num_passages, 900 + nbits + Nq, 4, 20, Nq)
     check_against_float64(hip, scorer.device_index, rows, Q, pids, f"nbits={nbits} Nq={Nq}")
+
+
+# ---- 2b. more than 64 passages per query: the dQ wave's second and third trips ----------------------------------------------
+def _place(pids, q, j, value):
+    """pids[q, j] = value; an edge passage (pid < 10) that sat there moves to a slot of the same list that holds an ordinary one."""
+    old = int(pids[q, j])
+    pids[q, j] = value
+    if 0 <= old < 10 and not bool((pids == old).any()):
+        spare = [i for i in range(4, pids.size(1) - 6) if int(pids[q, i]) >= 10 and i != 64]
+        pids[q, spare[0]] = old
+
+
+@pytest.mark.parametrize("k", [65, 130])
+@pytest.mark.parametrize("nbits", [2, 8])
+def test_backward_past_64_passages(hip, built, nbits, k):
+    """maxsim_gather_grad_q_kernel over the index loader: k = 65 leaves one row to the second trip, 130 two to the third.  One
+    passage is listed in every trip of query 0, query 1 ends in a tail of -1 slots."""
+    arrays, scorer, rows = built(nbits)
+    Nq = 32
+    Q, pids = seeded_case(hip.torch, rows, arrays.num_passages, 700 + nbits + k, 2, k, Nq)
+    for j in (3, 64, k - 1):
+        _place(pids, 0, j, 11)                 # one passage in every trip; the last slot of query 0 is live
+    for j in range(k - 5, k):
+        _place(pids, 1, j, -1)                 # the searcher's padding: a tail of empty slots
+    assert len(rows(11)) > 0 and int((pids[0] == 11).sum()) >= len({3, 64, k - 1}) and bool((pids[1, k - 5:] == -1).all())
+    check_against_float64(hip, scorer.device_index, rows, Q, pids, f"nbits={nbits} k={k}")
+    ops = hip.ops
+    _, _, am = ops.maxsim_index_fwd(scorer.device_index, Q.cuda(), pids.cuda())
+    am_k = am.cpu().numpy()
+    assert (am_k[0, k - 1] >= 0).all() and (am_k[1, k - 5:] == -1).all()
+    G = hip.torch.rand(am.shape, generator=hip.torch.Generator().manual_seed(Nq)) + 0.5
+    first = am_k.copy()
+    first[:, 64:] = -1                         # the rows past the first 64 carry gradient of their own
+    full, cut = restate_grad_q(rows, pids.numpy(), am_k, G.numpy()), restate_grad_q(rows, pids.numpy(), first, G.numpy())
+    assert np.abs(full[0] - cut[0]).max() > 0.05
+    dQ = ops.maxsim_index_bwd(scorer.device_index, pids.cuda(), am, G.cuda())
+    assert hip.torch.equal(dQ, ops.maxsim_index_bwd(scorer.device_index, pids.cuda(), am, G.cuda()))
 
 
 # ---- 3. against the search ------------------------------------------------------------------------------------------------

@@ -4,7 +4,8 @@
   repeated pids; dQ against the padded backward summed over k and against a float64 restatement from the kernel's own argmax;
 * fp16 store == fp32 store of the same values, bit for bit, forward and backward;
 * determinism, a non-default stream, the C ABI's error codes, 'flipr';
-* seeded random shapes against a float64 restatement, with the share of near-tie columns the comparison leaves out bounded;
+* seeded random shapes against a float64 restatement, with the share of near-tie columns the comparison leaves out bounded,
+  incl. k = 65 and 130 passages per query (further trips of the dQ wave's walk over a query's rows, 64 at a time);
 * end to end on an index built on the device, and the memory bound at the RAG training shape."""
 import ctypes as C
 from types import SimpleNamespace
@@ -312,6 +313,47 @@ def test_random_shapes_against_float64(hip, Ld):
         G = torch.rand(am.shape, generator=torch.Generator().manual_seed(Ld)) + 0.5
         dQ = ops.maxsim_gather_bwd(store.embeddings, pids.cuda(), am, G.cuda())
         grad_close(dQ.cpu(), restate_grad_q(Dd.numpy(), pids.numpy(), am_k, G.numpy()), f"Ld={Ld} {dtype} dQ")
+
+
+# ---- more than 64 passages per query: the dQ wave's second and third trips -------------------------------------------------
+@pytest.mark.parametrize("k", [65, 130])
+def test_backward_past_64_passages(hip, k):
+    """maxsim_gather_grad_q_kernel walks a query's k rows 64 at a time: k = 65 leaves one row to the second trip, 130 two to the
+    third.  One passage is listed in every trip of query 0 (its rows add up in dQ), query 1 ends in a tail of -1 slots."""
+    torch, ops, rag = hip.torch, hip.ops, hip.rag
+    n, P, Ld, Nq = 2, 40, 33, 40
+    Q, D, M, pids = rand_case(torch, 600 + k, n, k, P, Ld, Nq)
+    pids[0, 3] = pids[0, 64] = pids[0, k - 1] = 7       # one passage in every trip; the last slot of query 0 is live
+    pids[1, k - 5:] = -1                               # the searcher's padding: a tail of empty slots
+    assert bool(M[7].any()) and int((pids[0] == 7).sum()) >= len({3, 64, k - 1}) and bool((pids[1, k - 5:] == -1).all())
+    real_cols = np.ones(Nq, bool)
+    real_cols[Nq - Nq // 4:] = False           # (zeroed query rows tie exactly; they are compared in full below)
+    for dtype in ("float32", "float16"):
+        Dd = D if dtype == "float32" else D.half().float()
+        cm64, am64, gap = restate(Q.numpy(), Dd.numpy(), M.numpy(), pids.numpy())
+        sep = gap > GAP
+        share = float((~sep[:, :, real_cols]).mean())
+        print(f"k={k} {dtype}: {int((~sep[:, :, real_cols]).sum())} of {sep[:, :, real_cols].size} columns under the gap ({share:.2e})")
+        assert share <= MAX_FILTERED_SHARE
+        store = rag.PassageEmbeddingStore.from_padded(Dd, M, dtype=dtype)
+        assert str(store.dtype) == "torch." + dtype
+        out, colmax, am = ops.maxsim_gather_fwd(Q.cuda(), store.embeddings, store.mask, pids.cuda(), want_colmax=True)
+        am_k = am.cpu().numpy()
+        err = float(np.max(np.abs(colmax.cpu().numpy() - cm64)))
+        print(f"k={k} {dtype}: max|d colmax| {err:.3e}")
+        assert err <= SCORE_TOL
+        assert float(np.max(np.abs(out.cpu().numpy() - cm64.sum(-1)))) <= SCORE_TOL     # (an empty slot's -9999 * Nq is exact in fp32)
+        assert np.array_equal(am_k[sep], am64[sep])
+        assert np.array_equal(am_k[:, :, ~real_cols], am64[:, :, ~real_cols])        # exact 0-ties: the first real token
+        assert (am_k[pids.numpy() < 0] == -1).all() and (am_k[0, k - 1] >= 0).all()
+        G = torch.rand(am.shape, generator=torch.Generator().manual_seed(k)) + 0.5
+        dQ = ops.maxsim_gather_bwd(store.embeddings, pids.cuda(), am, G.cuda())
+        ref = restate_grad_q(Dd.numpy(), pids.numpy(), am_k, G.numpy())
+        grad_close(dQ.cpu(), ref, f"k={k} {dtype} dQ")
+        assert torch.equal(dQ, ops.maxsim_gather_bwd(store.embeddings, pids.cuda(), am, G.cuda()))
+        first = am_k.copy()
+        first[:, 64:] = -1                     # the rows past the first 64 carry gradient of their own
+        assert np.abs(ref[0] - restate_grad_q(Dd.numpy(), pids.numpy(), first, G.numpy())[0]).max() > 0.05
 
 
 # ---- end to end: index built on the device -> search -> gather -> differentiable score -------------------------------------

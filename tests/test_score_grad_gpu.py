@@ -2,7 +2,8 @@
 colbert_score_cross_differentiable, in_batch_negative_loss; FLMRModelForRetrieval(differentiable=True)):
 * against the reference's own autograd (tests/golden/score_grad.npz, make_golden_score_grad.py), exact ties included;
 * forward values bit-identical to the forward-only scorers;
-* seeded random shapes against a float64 restatement of the gradient that uses the kernel's argmax;
+* seeded random shapes against a float64 restatement of the gradient that uses the kernel's argmax, incl. more than 64 documents
+  per query row (the in-batch loss at batch x nway > 64: further trips of the dQ wave's document walk);
 * determinism, fp16 / bf16 inputs, a non-default stream, the FLMR model surface, the C ABI's error codes and the memory bound
   at the in-batch training shape."""
 import ctypes as C
@@ -171,6 +172,55 @@ def test_random_shapes_against_float64(hip, Ld, form):
         grad_close(dQ.cpu(), rQ, f"{form} Ld={Ld} Nq={Nq} dQ")
         grad_close(dD.cpu(), rD, f"{form} Ld={Ld} Nq={Nq} dD")
         assert (dD.cpu()[~M] == 0).all()
+
+
+# ---- more than 64 documents per query row: the dQ wave's second and third trips ---------------------------------------------
+# maxsim_grad_q_kernel walks a query row's documents 64 at a time.  FLMR's in-batch loss scores every query against
+# batch x nway documents: 128 at batch 64 with one negative, 160 at batch 32 with four.  (form, nQ, B, Ld, Nq, empty_doc): with
+# rand_case's all-padded last document the lone document of B = 65's second trip adds nothing (its winners are -1, skipped), so
+# that shape runs a second time with every document live.
+PAST_64 = [("cross", 3, 130, 33, 40, True), ("q_batch_1", 1, 65, 33, 40, True), ("q_batch_1", 1, 65, 33, 40, False),
+           ("q_batch_1", 1, 130, 70, 130, True), ("cross", 5, 193, 33, 32, True)]
+MAX_FILTERED_SHARE = 0.01      # the share of live columns the top-two gap rule may leave out of the winner comparison
+
+
+@pytest.mark.parametrize("form,nQ,B,Ld,Nq,empty_doc", PAST_64)
+def test_backward_past_64_documents(hip, form, nQ, B, Ld, Nq, empty_doc):
+    """B = 65 (one document in the second trip), 130 (two in the third) and 193 (one in the fourth).  With these seeds the gap
+    rule leaves out 0.01-0.11 % of the live columns, an fp32 sum in the kernel's order sits at 2-5 % of grad_close's bar, and one
+    dropped term (about 0.09 per component) is three orders of magnitude above it."""
+    torch, ops = hip.torch, hip.ops
+    cross = form == "cross"
+    Q, D, M = rand_case(torch, 4242 + B + Nq, nQ, B, Ld, Nq, empty_doc=empty_doc)
+    Qd, Dd, Md = Q.cuda(), D.cuda(), M.cuda()
+    out, colmax, am = ops.colbert_maxsim_fwd(Qd, Dd, Md, cross=cross, want_colmax=True)
+    cm64, am64, gap = restate(Q.numpy(), D.numpy(), M.numpy(), cross)
+    am_k = am.cpu().numpy().reshape(-1, Nq)
+    assert am_k.shape == (nQ * B, Nq)
+    assert np.max(np.abs(colmax.cpu().numpy().reshape(-1, Nq) - cm64)) <= SCORE_TOL
+    sep = gap > 1e-5
+    zero_cols = np.zeros(Nq, bool)
+    zero_cols[Nq - Nq // 4:] = True       # exact 0-ties: the first real token, as torch picks it
+    padded_doc = (np.arange(nQ * B) % B == B - 1) & empty_doc   # (its columns all hold the assigned -9999: gap 0, winner -1)
+    share = float((~sep[~padded_doc][:, ~zero_cols]).mean())
+    print(f"{form} B={B} Ld={Ld} Nq={Nq}: {share:.2e} of the live columns under the gap")
+    assert share <= MAX_FILTERED_SHARE
+    assert np.array_equal(am_k[sep], am64[sep])
+    assert np.array_equal(am_k[:, zero_cols], am64[:, zero_cols])
+    assert (am_k[padded_doc] == -1).all() and (am_k[~padded_doc] >= 0).all()
+    G = (torch.rand(am.shape, generator=torch.Generator().manual_seed(7)) + 0.5).cuda()
+    dQ, dD = ops.colbert_maxsim_bwd(Qd, Dd, am, G, cross=cross)
+    rQ, rD = restate_grad(Q.numpy(), D.numpy(), am_k, G.cpu().numpy(), cross)
+    grad_close(dQ.cpu(), rQ, f"{form} B={B} dQ")
+    grad_close(dD.cpu(), rD, f"{form} B={B} dD")
+    assert (dD.cpu()[~M] == 0).all()
+    dQ2, dD2 = ops.colbert_maxsim_bwd(Qd, Dd, am, G, cross=cross)
+    assert torch.equal(dQ, dQ2) and torch.equal(dD, dD2)
+    # the live documents past the first 64 carry gradient of their own: dQ differs from the sum over the first 64 alone
+    if B - int(empty_doc) > 64:
+        first = am_k.reshape(nQ, B, Nq).copy()
+        first[:, 64:] = -1
+        assert np.abs(rQ - restate_grad(Q.numpy(), D.numpy(), first.reshape(-1, Nq), G.cpu().numpy(), cross)[0]).max() > 0.05
 
 
 # ---- determinism, dtypes, streams -----------------------------------------------------------------------------------------

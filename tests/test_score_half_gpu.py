@@ -5,6 +5,7 @@ csrc/flmr_score_half.hip and the typed instantiations of csrc/flmr_score_grad.hi
   more than one tile, a ragged query tile, a second staging pass), with an all-padded document, interior mask holes, zeroed query
   rows, duplicated tokens, fp16 subnormals and -0.0;
 * an independent float64 restatement on the widened values with the tolerances of tests/test_score_grad_gpu.py;
+* the same at 130 documents per query row (cross and broadcast): the dQ wave's document walk past its first 64;
 * no widened copy of D is allocated; the in-batch loss, the FLMR model surface and the exhaustive search keep fp16 documents;
 * the typed C ABI's error codes, a non-default stream, non-contiguous and misaligned fp16 documents."""
 import ctypes as C
@@ -197,6 +198,44 @@ def test_half_forms_against_float64(hip, form, Ld):
             grad_close(dQ.cpu(), rQ, what + " dQ")
             grad_close(dD.cpu(), rD, what + " dD")
             assert (dD.cpu()[~c.Mcpu] == 0).all(), what
+
+
+# ---- 3b. more than 64 documents per query row ---------------------------------------------------------------------------
+@pytest.mark.parametrize("form,nQ,B,Ld,Nq", [("cross", 3, 130, 33, 40), ("q_batch_1", 1, 130, 70, 130)])
+def test_typed_backward_past_64_documents(hip, form, nQ, B, Ld, Nq):
+    """The dQ kernel walks a query row's documents 64 at a time: B = 130 is two full trips and a partial third.  Forward and
+    gradients bit-identical to the fp32 entry points on the widened operands, fp16 gradients that sum rounded once; dQ against
+    float64 with grad_close's bar."""
+    torch, ops = hip.torch, hip.ops
+    f16, f32 = torch.float16, torch.float32
+    cross = form == "cross"
+    Q32, Qh, Dh, M = half_case(torch, 4242 + B + Nq, nQ, B, Ld, Nq)
+    Q32, Qh, Dh, Md = Q32.cuda(), Qh.cuda(), Dh.cuda(), M.cuda()
+    G = (torch.rand(((nQ, B) if cross else (B,)) + (Nq,), generator=torch.Generator().manual_seed(7)) + 0.5).cuda()
+    for name, Q in (("hh", Qh), ("fh", Q32)):
+        what = (form, B, name)
+        r_out, r_colmax, r_am = ops.colbert_maxsim_fwd(Q.float(), Dh.float(), Md, cross=cross, want_colmax=True)
+        r_dQ, r_dD = ops.colbert_maxsim_bwd(Q.float(), Dh.float(), r_am, G, cross=cross)
+        out, colmax, am = ops.colbert_maxsim_fwd(Q, Dh, Md, cross=cross, want_colmax=True)
+        assert torch.equal(out, r_out) and torch.equal(colmax, r_colmax) and torch.equal(am, r_am), what
+        dQ, dD = ops.colbert_maxsim_bwd(Q, Dh, am, G, cross=cross, dq_dtype=Q.dtype, dd_dtype=f16)
+        assert dQ.dtype == Q.dtype and dD.dtype == f16
+        assert torch.equal(dQ, r_dQ.to(Q.dtype)) and torch.equal(dD, r_dD.to(f16)), what
+        dQ2, dD2 = ops.colbert_maxsim_bwd(Q, Dh, am, G, cross=cross, dq_dtype=Q.dtype, dd_dtype=f16)
+        assert torch.equal(dQ, dQ2) and torch.equal(dD, dD2), what
+        dQf, dDf = ops.colbert_maxsim_bwd(Q, Dh, am, G, cross=cross)
+        assert dQf.dtype == f32 and dDf.dtype == f32 and torch.equal(dQf, r_dQ) and torch.equal(dDf, r_dD), what
+        # fp16 dQ from fp16 D (the <_Float16, _Float16> dQ kernel) whatever Q's dtype
+        dQh, none = ops.colbert_maxsim_bwd(Q, Dh, am, G, cross=cross, need_dD=False, dq_dtype=f16)
+        assert none is None and torch.equal(dQh, r_dQ.to(f16)), what
+        am_k = am.cpu().numpy().reshape(-1, Nq)
+        rQ, rD = restate_grad(Q.float().cpu().numpy(), Dh.float().cpu().numpy(), am_k, G.cpu().numpy(), cross)
+        grad_close(dQf.cpu(), rQ, f"{what} dQ")
+        grad_close(dDf.cpu(), rD, f"{what} dD")
+        assert (dDf.cpu()[~M] == 0).all(), what
+        first = am_k.reshape(nQ, B, Nq).copy()
+        first[:, 64:] = -1                       # the documents past the first 64 carry gradient of their own
+        assert np.abs(rQ - restate_grad(Q.float().cpu().numpy(), Dh.float().cpu().numpy(), first.reshape(-1, Nq), G.cpu().numpy(), cross)[0]).max() > 0.05
 
 
 # ---- 4. no widened copy -------------------------------------------------------------------------------------------------
