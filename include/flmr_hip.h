@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FLMR_ABI_VERSION 11
+#define FLMR_ABI_VERSION 12
 
 typedef enum flmr_status {
     FLMR_OK = 0,
@@ -52,7 +52,7 @@ int flmr_device_count(int* count);
  * of the library; afterwards the switches change only through this call (value NULL or "" clears a switch).  Each switch
  * takes exactly the values named here (FLMR_S0_IMPL = qs1 | f16 | f16rs | f32 | mfma | valu; FLMR_S1_IMPL = scan | slots | image;
  * FLMR_S2_IMPL = xcda | xcd | walk | lds, plus regs | ldsb in FLMR_EXPERIMENTAL_VARIANTS builds; FLMR_S3_IMPL = qs | lean | cw |
- * cwregs | dma | regs | f32; FLMR_CAND_IMPL = atomic; FLMR_SCORE_IMPL = valu; FLMR_ROW_CAP = an integer; the others are set by
+ * cwregs | dma | regs | f32; FLMR_CAND_IMPL = atomic | bitmaps; FLMR_SCORE_IMPL = valu; FLMR_ROW_CAP = an integer; the others are set by
  * any value): any other value returns FLMR_ERR_INVALID with the accepted values in flmr_last_error(), and such a value in the
  * environment makes flmr_index_open, flmr_searcher_create and the op-level calls that consult switches fail the same way.
  * Op-level entry points read the switches when they are called; a searcher snapshots them at flmr_searcher_create and plans
@@ -68,7 +68,10 @@ int flmr_device_count(int* count);
  * queue form first, the slot form for the queries that one hands over, and beyond the list-scatter forms' limits -- more than 1024
  * surviving centroids, lists far longer than the probed cells' -- the dense forms of flmr_stage1_dense.hip: fp16 images of the
  * query's score rows in LDS, upper-bound keys for every candidate, the band around the cut rescored exactly; the exact form alone
- * when the rows do not fit; image: the queries beyond the images go to the code scan).
+ * when the rows do not fit; image: the queries beyond the images go to the code scan); FLMR_CAND_IMPL = atomic | bitmaps (atomic: the
+ * first candidate generation, global atomics into one bitmap; bitmaps: the queue form of the list scatter marks the probed cells'
+ * candidate bitmap for every query -- by default it skips that for a query whose surviving centroids are all probed cells, see
+ * flmr_searcher_cand_bitmaps; results are the same, bit for bit).
  * Variants of one arithmetic are bit-identical to each other, the arithmetics agree to fp32 roundoff (tests/test_hip_parity.py).
  * One switch is a capacity, not a variant: FLMR_ROW_CAP = score rows a searcher keeps per query (64 .. 65535, default 16384,
  * never more than K).  The default path stores the centroid scores of a query only for the centroids that pass
@@ -245,6 +248,16 @@ typedef enum flmr_tap {
 } flmr_tap_t;
 int flmr_searcher_tap(flmr_searcher_t* searcher, int32_t what, int32_t query, void* host_out, int64_t capacity,
                       int64_t* count);
+/* What became of the candidate bitmap of `query` of the LAST batch on the list-scatter path (synchronises the stream).  *state:
+ * 0 marked in the scatter pass (some surviving centroid is not a probed cell, the query is empty, FLMR_CAND_IMPL=bitmaps, or another
+ * form than the queue form finished the query -- see FLMR_TAP_STAGE1_FORM); 1 skipped: every surviving centroid is a probed cell, so
+ * every passage of a surviving list is a candidate, and the query kept at least ndocs hit candidates -- nothing in the search read the
+ * bitmap; 2 skipped in the pass and marked from the probed cells afterwards, inside the search, because fewer than ndocs hit candidates
+ * were left and the others had to be appended; -1 the batch did not plan the fast forms (FLMR_S1_IMPL = scan | slots, FLMR_CAND_IMPL =
+ * atomic, FLMR_S1_NO_HITMAP, several column tiles).  Reading FLMR_TAP_CANDIDATES after a batch marks the skipped bitmaps first: until
+ * the next batch or phase 1 starts, the searcher keeps the last batch's probed cells, flags, plan words and key counters, hit bitmaps
+ * and per-chunk hit counts for that. */
+int flmr_searcher_cand_bitmaps(flmr_searcher_t* searcher, int32_t query, int32_t* state);
 
 /* By default the per-query centroid-score table is kept SPARSE (only the rows of centroids that pass the threshold are
  * stored; stage 2 and the cell probe recompute what they need).  Enable the full table before a batch whose

@@ -21,7 +21,7 @@ FLMR_F32, FLMR_F16 = 0, 1   # store_dtype of flmr_maxsim_gather_fwd / _bwd; q_dt
 (TAP_CENTROID_SCORES, TAP_IDX_BITS, TAP_CELLS, TAP_CANDIDATES, TAP_STAGE1, TAP_STAGE2, TAP_DOC_SCORES, TAP_Q_ERR,
  TAP_Q_ERR_SUM, TAP_STAGE1_FORM) = range(10)
 NUM_STAGES = 9
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class FlmrNativeError(RuntimeError):
@@ -148,6 +148,7 @@ _SIGS = {
     "flmr_compress_f16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "flmr_searcher_tap": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "flmr_searcher_cand_bitmaps": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "flmr_searcher_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
     "flmr_searcher_set_full_table": (C.c_int, [C.c_void_p, C.c_int32]),
     "flmr_searcher_set_numerics": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -232,10 +232,28 @@ __global__ __launch_bounds__(64 * PLAN_WAVES) void cand_plan_kernel(flmr_cand_ar
         if (m != FLMR_S1D_SKIP) atomicOr(a.s1d_any + 1, 1);
     }
     if (!a.hit_valid[b] || nl > 512 || nq > 512) {   // (block-uniform) not a list-scatter query / more lists than the fast forms index
-        if (tid == 0) *plan = 1;
+        if (tid == 0) { *plan = 1; if (a.implied) a.implied[b] = 0; }
         return;
     }
-    const int ntot = nl + nq;
+    // "cells imply candidates" (flmr_cand_args::implied): every surviving centroid is a probed cell of this non-empty query.  Then
+    // the candidate bitmap covers the hit bitmap whatever else is in it, and neither the sample below nor the queue form marks it:
+    // H is the count of hit bits, Q the pairs of the passages in `sb` -- the numbers the marked bitmap gives.
+    bool imp = false;
+    if (a.implied) {   // (block-uniform)
+        const int qlen = a.q_lens ? a.q_lens[b] : a.nq_cand;
+        for (int e = tid; e < nl; e += 64 * PLAN_WAVES) cb[e] = (uint32_t)a.cells[(size_t)b * a.max_cells + e];   // (nl <= 512)
+        __syncthreads();
+        int missing = 0;
+        if (tid < nq) {
+            const uint32_t c = (uint32_t)a.qual[(size_t)b * a.qmax + tid];
+            missing = 1;
+            for (int e = 0; e < nl; e++) missing &= cb[e] != c;
+        }
+        imp = !__syncthreads_or(missing) && qlen > 0 && a.nq_cand > 0 && !a.force_bitmaps;
+        if (tid == 0) a.implied[b] = imp ? 1 : 0;
+    }
+    const int nlm = imp ? 0 : nl;   // the probed-cell lists the sample marks
+    const int ntot = nlm + nq;
     const int mine = wave < ntot ? (ntot - wave + PLAN_WAVES - 1) / PLAN_WAVES : 0;   // lists of this wave (<= 64)
     // lane j: list wave + 16 j of the query (cells first, then the surviving lists)
     int64_t beg = 0;
@@ -243,8 +261,8 @@ __global__ __launch_bounds__(64 * PLAN_WAVES) void cand_plan_kernel(flmr_cand_ar
     size_t trow = 0;
     if (lane < mine) {
         const int l = wave + PLAN_WAVES * lane;
-        is_cell = l < nl;
-        const int c = is_cell ? a.cells[(size_t)b * a.max_cells + l] : a.qual[(size_t)b * a.qmax + (l - nl)];
+        is_cell = l < nlm;
+        const int c = is_cell ? a.cells[(size_t)b * a.max_cells + l] : a.qual[(size_t)b * a.qmax + (l - nlm)];
         beg = a.ivf_offsets[c];
         trow = (size_t)c * (a.nchunks + 1);
     }
@@ -282,7 +300,7 @@ __global__ __launch_bounds__(64 * PLAN_WAVES) void cand_plan_kernel(flmr_cand_ar
             for (uint32_t x = sv + (u < PLAN_REGS ? 64u : 0u) + lane; x < ev; x += 64) {
                 const int p = a.ivf_pids[bg + x] - pid0;
                 if (!count) mark(p, cell);
-                else if (!cell) q += (int)((cb[p >> 5] & sb[p >> 5]) >> (p & 31)) & 1;
+                else if (!cell) q += (int)(((imp ? ~0u : cb[p >> 5]) & sb[p >> 5]) >> (p & 31)) & 1;
             }
         };
         int q = 0;
@@ -292,11 +310,11 @@ __global__ __launch_bounds__(64 * PLAN_WAVES) void cand_plan_kernel(flmr_cand_ar
         for (int u = 0; u < mine; u++) rest(u, false, q);
         __syncthreads();
         int h = 0;
-        for (int w = tid; w < CAND_CHUNK_WORDS; w += 64 * PLAN_WAVES) h += __popc(cb[w] & hb[w]);
+        for (int w = tid; w < CAND_CHUNK_WORDS; w += 64 * PLAN_WAVES) h += __popc((imp ? ~0u : cb[w]) & hb[w]);
         // the pairs the queue form would queue: (surviving list, passage) with the passage a candidate that holds several of them
 #pragma unroll
         for (int u = 0; u < PLAN_REGS; u++)
-            if (r[u] >= 0 && !((cellmask >> u) & 1ull)) q += (int)((cb[r[u] >> 5] & sb[r[u] >> 5]) >> (r[u] & 31)) & 1;
+            if (r[u] >= 0 && !((cellmask >> u) & 1ull)) q += (int)(((imp ? ~0u : cb[r[u] >> 5]) & sb[r[u] >> 5]) >> (r[u] & 31)) & 1;
         for (int u = 0; u < mine; u++) rest(u, true, q);
         h = cf_wave_sum_early(h);
         q = cf_wave_sum_early(q);
@@ -404,6 +422,50 @@ __device__ unsigned long long s1s_prof[12];
 #define S1S_STAMP(k) do { } while (0)
 #endif
 
+// The candidate bitmap words and the candidate count of chunk `ch` of query b from the probed cells' lists alone, for a query whose
+// queue-form pass went without them (flmr_cand_args::implied).  `cb`: CAND_CHUNK_WORDS words of LDS, zero on entry and on exit;
+// any block size that is a multiple of 64; the same words and count as the marking passes of the scatter forms write.
+__device__ __forceinline__ void cand_mark_cells_chunk(const flmr_cand_args& a, int b, int ch, uint32_t* cb, int* cnt_lds) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const int nl = a.ncell[b], pid0 = ch * CAND_CHUNK_PIDS;
+    if (tid == 0) *cnt_lds = 0;
+    for (int l = wave; l < nl; l += nwaves) {   // one list slice per wave at a time, lanes over its entries
+        const int c = a.cells[(size_t)b * a.max_cells + l];
+        const int64_t beg = a.ivf_offsets[c];
+        const uint32_t s = a.chunk_tab[(size_t)c * (a.nchunks + 1) + ch], e = a.chunk_tab[(size_t)c * (a.nchunks + 1) + ch + 1];
+        for (uint32_t x = s + lane; x < e; x += 64) {
+            const int pid = a.ivf_pids[beg + x] - pid0;
+            atomicOr(&cb[pid >> 5], 1u << (pid & 31));
+        }
+    }
+    __syncthreads();
+    int cnt = 0;
+    for (int w = tid; w < CAND_CHUNK_WORDS; w += blockDim.x) {
+        const int64_t gw = (int64_t)ch * CAND_CHUNK_WORDS + w;
+        if (gw < a.words) {
+            a.cand_bits[(size_t)b * a.words + gw] = cb[w];
+            cnt += __popc(cb[w]);
+        }
+        cb[w] = 0u;
+    }
+    if (cnt) atomicAdd(cnt_lds, cnt);
+    __syncthreads();
+    if (tid == 0) a.chunk_cnt[(size_t)b * a.nchunks + ch] = *cnt_lds;
+    __syncthreads();
+}
+
+// the same for every (query, chunk) of the last batch that went without, after the search (flmr_launch_cand_emit_all)
+__global__ __launch_bounds__(256) void cand_deferred_bitmaps_kernel(flmr_cand_args a) {
+    __shared__ uint32_t cb[CAND_CHUNK_WORDS];
+    __shared__ int cnt_lds;
+    const int b = blockIdx.x;
+    if (flmr_cand_bitmaps_state(a.implied[b], a.fast_state[FLMR_FAST_HDR + b], a.fast_state[FLMR_FAST_HDR + a.nqueries + b], a.n_select) != 1)
+        return;   // (block-uniform)
+    for (int w = threadIdx.x; w < CAND_CHUNK_WORDS; w += 256) cb[w] = 0u;
+    __syncthreads();
+    cand_mark_cells_chunk(a, b, blockIdx.y, cb, &cnt_lds);
+}
+
 // A workgroup takes `cpb` consecutive chunks of one query: the list ids and offsets are fetched once, and only the chunk
 // table entry that ends the NEXT chunk's slice is loaded per chunk (a chunk's slice starts where the previous one ended),
 // requested a whole chunk ahead.
@@ -432,7 +494,16 @@ __global__ __launch_bounds__(64 * S1S_WAVES) void cand_mark_score_kernel(flmr_ca
         if (blockIdx.y == 0 && tid == 0) {
             if (r == 0 || r == 3) a.key_count[b] = a.fast_state[FLMR_FAST_HDR + a.nqueries + b];
         }
-        if (r == 0 || r == 3) return;   // done by the queue form / by the small-dense form
+        if (r == 0 || r == 3) {   // done by the queue form / by the small-dense form
+            // ... without the candidate bitmap (flmr_cand_args::implied), and with fewer hit candidates than the selection keeps:
+            // cand_emit_kernel, the next launch, appends the other candidates from the bitmap, so it is marked here
+            if (a.implied && flmr_cand_bitmaps_state(a.implied[b], r, a.fast_state[FLMR_FAST_HDR + a.nqueries + b], a.n_select) == 2) {
+                cb[tid] = 0u;  // CAND_CHUNK_WORDS == blockDim.x
+                __syncthreads();
+                for (int ch = ch0; ch < ch_end; ch++) cand_mark_cells_chunk(a, b, ch, cb, &s_base);
+            }
+            return;
+        }
     }
     const int nl = a.ncell[b];
     const bool scatter = a.hit_valid[b] != 0;
@@ -856,8 +927,12 @@ __device__ unsigned long long cf_prof[12];
 #define CF_STAMP(k) do { } while (0)
 #endif
 
-template <bool F16>
-__global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args a, int cpb) {
+// IMP: the query's cells imply its candidates (flmr_cand_args::implied; block-uniform, so the kernel below holds both bodies and a
+// workgroup runs one).  Every pair of a surviving list is then a candidate's, and the body leaves out what only the candidate bitmap
+// needs: the probed cells' slices (mc, raw_c and their chunk-table reads), the marks and reads of `cb` and its clearing, the
+// cand_bits and chunk_cnt stores; the chunk's hit count is popc(hb).  Nothing is added: same barriers, same waits, the same keys.
+template <bool F16, bool IMP>
+__device__ __forceinline__ void cand_fast_body(const flmr_cand_args& a, int cpb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint32_t* bm = reinterpret_cast<uint32_t*>(smem);                          // [3][candidate | hit | several][CAND_CHUNK_WORDS]
     uint32_t* kbuf = bm + 9 * CAND_CHUNK_WORDS;                                // [2][CF_KCAP] list << 15 | passage inside the chunk
@@ -878,7 +953,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
     }
     const int ch0 = blockIdx.y * cpb;
     const int ch_end = ch0 + cpb < a.nchunks ? ch0 + cpb : a.nchunks;
-    cf_slices mc = cf_load_slices(a.cells + (size_t)b * a.max_cells, nl, wave, lane, a.ivf_offsets, a.chunk_tab, a.nchunks, ch0);
+    cf_slices mc = cf_load_slices(a.cells + (size_t)b * a.max_cells, IMP ? 0 : nl, wave, lane, a.ivf_offsets, a.chunk_tab, a.nchunks, ch0);   // (IMP: no list, nothing loaded)
     cf_slices mq = cf_load_slices(a.qual + (size_t)b * a.qmax, nq, wave, lane, a.ivf_offsets, a.chunk_tab, a.nchunks, ch0);
     const int init = s1s_enc(-9999.0f);
     const int qlen = a.q_lens ? a.q_lens[b] : a.nq_cand;
@@ -902,7 +977,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
     };
     int raw_c[CF_FC], raw_q[CF_FQ], raw_qn[CF_FQ];
 #pragma unroll
-    for (int u = 0; u < CF_FC; u++) raw_c[u] = issue1(mc, mc.n, u, mc.s, mc.e);
+    for (int u = 0; u < CF_FC; u++) raw_c[u] = IMP ? 0 : issue1(mc, mc.n, u, mc.s, mc.e);
 #pragma unroll
     for (int u = 0; u < CF_FQ; u++) { raw_q[u] = issue1(mq, mq.n, u, mq.s, mq.e); raw_qn[u] = 0; }
     // the stage-1 score of a passage whose only surviving centroid is this lane's list (see the slot kernel)
@@ -952,7 +1027,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
         uint32_t* const qu = queue + r3 * CF_QCAP;
         uint32_t mc_e2 = 0, mq_e2 = 0;
         if (ch + 1 < ch_end) {   // the end of the NEXT chunk's slices
-            if (lane < mc.n) mc_e2 = a.chunk_tab[(size_t)mc.c * (a.nchunks + 1) + ch + 2];
+            if (!IMP && lane < mc.n) mc_e2 = a.chunk_tab[(size_t)mc.c * (a.nchunks + 1) + ch + 2];
             if (lane < mq.n) mq_e2 = a.chunk_tab[(size_t)mq.c * (a.nchunks + 1) + ch + 2];
         }
         CF_STAMP(0);
@@ -970,7 +1045,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
             asm volatile("" : "+s"(ncl), "+s"(nql));
 #pragma unroll
             for (int u = 0; u < CF_FC; u++) {
-                if (u < ncl) {
+                if (!IMP && u < ncl) {
                     const uint32_t sv = (uint32_t)__builtin_amdgcn_readlane((int)mc.s, u), ev = (uint32_t)__builtin_amdgcn_readlane((int)mc.e, u);
                     if (sv + lane < ev) {
                         const int p = raw_c[u] - pid0;
@@ -986,7 +1061,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
                     }
                 }
             }
-            for (int u = CF_FC; u < mc.n; u++) {   // rare: more than CF_FC lists per wave
+            for (int u = CF_FC; !IMP && u < mc.n; u++) {   // rare: more than CF_FC lists per wave
                 const uint32_t sv = (uint32_t)__builtin_amdgcn_readlane((int)mc.s, u), ev = (uint32_t)__builtin_amdgcn_readlane((int)mc.e, u);
                 const int32_t* ptr = list_ptr(mc, u);
                 for (uint32_t x = sv + lane; x < ev; x += 64) {
@@ -1030,16 +1105,16 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
             for (int h = 0; h < CAND_CHUNK_WORDS / CF_THREADS; h++) {
                 const int w = tid + h * CF_THREADS;
                 const int64_t gw = (int64_t)ch * CAND_CHUNK_WORDS + w;
-                uint32_t cw = cb[w];
+                uint32_t cw = IMP ? ~0u : cb[w];   // (IMP: every hit bit is a candidate's)
                 const uint32_t hw = hb[w];
                 if (gw < a.words) {
-                    a.cand_bits[(size_t)b * a.words + gw] = cw;
+                    if (!IMP) a.cand_bits[(size_t)b * a.words + gw] = cw;
                     a.hit_bits[(size_t)b * a.words + gw] = hw;
                 } else {
                     cw = 0u;
                 }
-                mine += __popc(cw) | (__popc(cw & hw) << 16);
-                bm[(rp * 3 + 0) * CAND_CHUNK_WORDS + w] = 0u;
+                mine += (IMP ? 0 : __popc(cw)) | (__popc(cw & hw) << 16);
+                if (!IMP) bm[(rp * 3 + 0) * CAND_CHUNK_WORDS + w] = 0u;   // (IMP: never marked)
                 bm[(rp * 3 + 1) * CAND_CHUNK_WORDS + w] = 0u;
                 bm[(rp * 3 + 2) * CAND_CHUNK_WORDS + w] = 0u;
             }
@@ -1051,7 +1126,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
                     const uint32_t tot = (uint32_t)atomicExch(&s_tot, 0);
                     s_arr = 0;
                     const int cnt = (int)(tot & 0xffffu), nh = (int)(tot >> 16);
-                    a.chunk_cnt[(size_t)b * a.nchunks + ch] = cnt;
+                    if (!IMP) a.chunk_cnt[(size_t)b * a.nchunks + ch] = cnt;
                     a.chunk_hits[(size_t)b * a.nchunks + ch] = nh;
                     st[r3].nh = nh;
                     if (nh > CF_KCAP) { s_abort[ch & 1] = 1; *redo = 2; }
@@ -1068,7 +1143,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
                 int ncp = mc.n, nqp = mq.n;
                 asm volatile("" : "+s"(ncp), "+s"(nqp));
 #pragma unroll
-                for (int u = 0; u < CF_FC; u++) raw_c[u] = issue1(mc, ncp, u, mc.e, mc_e2);
+                for (int u = 0; u < CF_FC; u++) raw_c[u] = IMP ? 0 : issue1(mc, ncp, u, mc.e, mc_e2);
 #pragma unroll
                 for (int u = 0; u < CF_FQ; u++) raw_qn[u] = issue1(mq, nqp, u, mq.e, mq_e2);
             }
@@ -1078,7 +1153,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
                 bool single = false, several = false;
                 if (p >= 0) {
                     const uint32_t bit = 1u << (p & 31);
-                    const bool cand = (cb[p >> 5] & bit) != 0u, sev = (mb[p >> 5] & bit) != 0u;
+                    const bool cand = IMP || (cb[p >> 5] & bit) != 0u, sev = (mb[p >> 5] & bit) != 0u;
                     single = cand && !sev;
                     several = cand && sev;
                 }
@@ -1113,7 +1188,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
                         const bool ok = sv + lane < ev;
                         pp[u] = ok ? p : -1;
                         const int w = ok ? p >> 5 : 0;
-                        cw_[u] = cb[w]; mw_[u] = mb[w];
+                        cw_[u] = IMP ? ~0u : cb[w]; mw_[u] = mb[w];
                     }
                 }
                 uint64_t ms[CF_FQ];
@@ -1250,6 +1325,12 @@ __global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args
         atomicAdd(&cf_prof[11], 1ull);
     }
 #endif
+}
+
+template <bool F16>
+__global__ __launch_bounds__(CF_THREADS, 2) void cand_fast_kernel(flmr_cand_args a, int cpb) {
+    if (a.implied && a.implied[blockIdx.x]) cand_fast_body<F16, true>(a, cpb);   // (block-uniform; read by the body only for a query planned for this form)
+    else cand_fast_body<F16, false>(a, cpb);
 }
 
 // ---- kernel A-3: the SMALL-DENSE form of the scatter kernel ------------------------------------------------------------------
@@ -1735,6 +1816,8 @@ int flmr_launch_candidates_chunked(const flmr_cand_args& a, hipStream_t st) {
 
 // the ascending candidate lists of every query of the last batch (FLMR_TAP_CANDIDATES after a scatter-mode search)
 int flmr_launch_cand_emit_all(const flmr_cand_args& a, hipStream_t st) {
+    if (a.scatter && a.fast_state && a.implied)   // the candidate bitmaps of the queries whose pass went without them
+        hipLaunchKernelGGL(cand_deferred_bitmaps_kernel, dim3(a.nqueries, a.nchunks), dim3(256), 0, st, a);
     hipLaunchKernelGGL(cand_emit_kernel, dim3(a.nqueries, a.nchunks), dim3(1024), 0, st, a.cand_bits, a.hit_bits, a.words,
                        a.chunk_cnt, a.nchunks, a.cand, a.cand_cap, a.cand_hit, a.cand_count, a.overflow, nullptr, nullptr, nullptr, nullptr,
                        nullptr, 0, 0, 0);

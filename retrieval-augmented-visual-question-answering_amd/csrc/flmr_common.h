@@ -59,6 +59,8 @@ struct flmr_options {
                               // kernel for long queries) | f32 (fp32-MFMA kernel)
     bool full_table;          // FLMR_FULL_TABLE: keep the whole centroid-score table
     bool cand_atomic;         // FLMR_CAND_IMPL=atomic: first candidate-generation implementation
+    bool cand_bitmaps;        // FLMR_CAND_IMPL=bitmaps: the queue form marks the probed cells' candidate bitmap for every query (it skips it
+                              // by default where every surviving centroid is a probed cell: flmr_cand_args::implied)
     bool s1_no_hitmap;        // FLMR_S1_NO_HITMAP: no hit prefilter
     bool s0_staged;           // FLMR_S0_STAGED: staged epilogue for every tile
     bool s3_no_multiq;        // FLMR_S3_NO_MULTIQ: single-tile MaxSim kernel for long queries too
@@ -280,10 +282,26 @@ struct flmr_cand_args {
     int32_t* s1d_mode; int32_t* s1d_scan_skip; int32_t* s1d_any; int32_t s1d_img_rows, s1d_exact_too;
     int32_t* row_ovf;   // [nqueries] out: 1 = the query has more surviving centroids than compact score rows (qmax): its stage 1 is
                         // recomputed from the fp16 centroids (flmr_launch_filter_stage1_recompute); NULL on the full-table path
+    // "cells imply candidates", per query [b], written by cand_plan_kernel: 1 = the query is non-empty, hit_valid holds and every
+    // surviving centroid is one of its probed cells, so every passage of a surviving list is a candidate by that same list.  The queue
+    // form then neither loads the probed cells' lists nor writes cand_bits / chunk_cnt for the query: nothing in the search reads them
+    // unless the query ends with fewer than n_select hit candidates, and then cand_mark_score_kernel (which knows the final count) marks
+    // them from `cells` before cand_emit_kernel appends the other candidates.  Readers outside the search (FLMR_TAP_CANDIDATES) get
+    // them from flmr_launch_cand_emit_all, which marks them first for the queries that went without (flmr_cand_bitmaps_state == 1):
+    // for that, cells / ncell, implied, fast_state, hit_bits and chunk_hits of the last batch stay untouched until the next batch or
+    // phase 1 starts.  NULL (or force_bitmaps, FLMR_CAND_IMPL=bitmaps): the cells are marked for every query.
+    int32_t* implied; int32_t force_bitmaps;
 };
+// what became of query b's candidate bitmap on the list-scatter path (flmr_searcher_cand_bitmaps): 0 = marked in the scatter pass (flag
+// clear, or another form than the queue form finished the query), 1 = never needed inside the search (skipped), 2 = skipped in the
+// pass and marked afterwards inside the search (fewer than n_select hit candidates)
+__host__ __device__ static inline int flmr_cand_bitmaps_state(int implied, int plan_word, int key_count, int n_select) {
+    if (!implied || plan_word != 0) return 0;
+    return key_count >= n_select ? 1 : 2;
+}
 int flmr_launch_candidates_chunked(const flmr_cand_args& a, hipStream_t st);
 int flmr_launch_qualifying(const flmr_cand_args& a, hipStream_t st);   // list + ranks + compact score rows only
-int flmr_launch_cand_emit_all(const flmr_cand_args& a, hipStream_t st);
+int flmr_launch_cand_emit_all(const flmr_cand_args& a, hipStream_t st);   // (marks the candidate bitmaps a flagged query went without first)
 int flmr_build_chunk_table(const int32_t* ivf_pids, const int64_t* ivf_offsets, int K, int64_t num_passages,
                            uint32_t** out_tab, int32_t* out_nchunks);
 // passage bitmap of the union of the surviving centroids' IVF lists (+ per-query validity flag)

@@ -24,13 +24,13 @@ static const opt_value kS2[] = {{"xcda", (int)s2_sw::xcda}, {"xcd", (int)s2_sw::
 };
 static const opt_value kS3[] = {{"qs", (int)s3_sw::qs}, {"lean", (int)s3_sw::lean}, {"cw", (int)s3_sw::cw}, {"cwregs", (int)s3_sw::cwregs},
                                 {"dma", (int)s3_sw::dma}, {"regs", (int)s3_sw::regs}, {"f32", (int)s3_sw::f32}};
-static const opt_value kAtomic[] = {{"atomic", 1}};
+static const opt_value kCand[] = {{"atomic", 1}, {"bitmaps", 2}};
 static const opt_value kValu[] = {{"valu", 1}};
 static const opt_value kInt[] = {{"#", 0}};
 #define N_(a) (int)(sizeof(a) / sizeof(a[0]))
 enum { O_S0, O_FULL_TABLE, O_CAND, O_NO_HITMAP, O_S1, O_S2, O_S0_STAGED, O_NO_MULTIQ, O_S3, O_SCORE, O_POISON, O_ROW_CAP, O_COUNT };
 static const opt_spec kOpts[O_COUNT] = {
-    {"FLMR_S0_IMPL", kS0, N_(kS0)}, {"FLMR_FULL_TABLE", nullptr, 0}, {"FLMR_CAND_IMPL", kAtomic, 1}, {"FLMR_S1_NO_HITMAP", nullptr, 0},
+    {"FLMR_S0_IMPL", kS0, N_(kS0)}, {"FLMR_FULL_TABLE", nullptr, 0}, {"FLMR_CAND_IMPL", kCand, N_(kCand)}, {"FLMR_S1_NO_HITMAP", nullptr, 0},
     {"FLMR_S1_IMPL", kS1, N_(kS1)}, {"FLMR_S2_IMPL", kS2, N_(kS2)}, {"FLMR_S0_STAGED", nullptr, 0}, {"FLMR_S3_NO_MULTIQ", nullptr, 0},
     {"FLMR_S3_IMPL", kS3, N_(kS3)}, {"FLMR_SCORE_IMPL", kValu, 1}, {"FLMR_POISON", nullptr, 0}, {"FLMR_ROW_CAP", kInt, 1}};
 #undef N_
@@ -64,7 +64,7 @@ static int parse_opt(int id, const char* value, flmr_options* o, char* err, size
     switch (id) {
         case O_S0: o->s0 = (s0_sw)v; break;
         case O_FULL_TABLE: o->full_table = true; break;
-        case O_CAND: o->cand_atomic = true; break;
+        case O_CAND: o->cand_atomic = v == 1; o->cand_bitmaps = v == 2; break;
         case O_NO_HITMAP: o->s1_no_hitmap = true; break;
         case O_S1: o->s1 = (s1_sw)v; break;
         case O_S2: o->s2 = (s2_sw)v; break;
@@ -84,7 +84,7 @@ static void clear_opt(int id, flmr_options* o) {
     switch (id) {
         case O_S0: o->s0 = d.s0; break;
         case O_FULL_TABLE: o->full_table = false; break;
-        case O_CAND: o->cand_atomic = false; break;
+        case O_CAND: o->cand_atomic = false; o->cand_bitmaps = false; break;
         case O_NO_HITMAP: o->s1_no_hitmap = false; break;
         case O_S1: o->s1 = d.s1; break;
         case O_S2: o->s2 = d.s2; break;

@@ -84,6 +84,7 @@ struct flmr_searcher {
     // how many keys the selection reads, and which queries are left to the round-5 scan
     int32_t* s1d_any; int32_t* s1d_mode; int32_t* s1d_band; int32_t* s1d_band_count; float* s1d_err; int32_t* s1d_in_count; int32_t* s1d_scan_skip;
     int32_t s1d_img_rows;       // score-row images the LDS form holds (0: no dense form on this index)
+    int32_t* cand_implied;      // flmr_cand_args::implied ([max_queries])
     int32_t* cand_fast;         // flmr_cand_args::fast_state ([FLMR_FAST_HDR + 2 * max_queries]; the header words live as long as the searcher)
     // last call (for taps)
     int32_t last_nqueries, last_ncol, last_ndocs;
@@ -266,6 +267,7 @@ extern "C" int flmr_searcher_create(const flmr_index_t* ix, int32_t max_queries,
                 s->s3_colmax_cap = 0;
         }
     }
+    WS(cand_implied, B, WS_ZERO);                               // flag: 0 = the candidate bitmap is marked in the scatter pass
     // (plan words and key counters, written for every query of a batch before they are read; zeroed once here as before)
     WS(cand_fast, 2 * B + FLMR_FAST_HDR, WS_ZERO);
 #undef WS
@@ -656,6 +658,7 @@ static int stage_cand_s1(run_ctx& c, uint64_t* out_keys) {
             ca.s1d_mode = s->s1d_mode; ca.s1d_scan_skip = s->s1d_scan_skip; ca.s1d_any = s->s1d_any;
             ca.s1d_img_rows = pl.img_rows;
             ca.s1d_exact_too = pl.exact_too ? 1 : 0;
+            ca.implied = s->cand_implied; ca.force_bitmaps = s->opt.cand_bitmaps ? 1 : 0;
         }
     }
     if (pl.chunked) {
@@ -975,5 +978,19 @@ extern "C" int flmr_searcher_tap(flmr_searcher_t* s, int32_t what, int32_t q, vo
     *count = n;
     if (n > capacity) FLMR_FAIL(FLMR_ERR_CAPACITY, "tap needs %lld elements, capacity %lld", (long long)n, (long long)capacity);
     if (n) FLMR_HIP(hipMemcpy(host_out, src, (size_t)n * esz, hipMemcpyDeviceToHost));
+    return FLMR_OK;
+}
+
+extern "C" int flmr_searcher_cand_bitmaps(flmr_searcher_t* s, int32_t q, int32_t* state) {
+    if (!s || !state) FLMR_FAIL(FLMR_ERR_INVALID, "NULL argument");
+    if (q < 0 || q >= s->last_nqueries) FLMR_FAIL(FLMR_ERR_INVALID, "query %d outside the last batch (%d)", q, s->last_nqueries);
+    FLMR_HIP(hipStreamSynchronize(s->last_stream));
+    *state = -1;
+    if (!(s->last_plan.scatter && s->last_ca.fast_state && s->last_ca.implied)) return FLMR_OK;
+    int32_t imp = 0, word = 0, kc = 0;
+    FLMR_HIP(hipMemcpy(&imp, s->cand_implied + q, 4, hipMemcpyDeviceToHost));
+    FLMR_HIP(hipMemcpy(&word, s->cand_fast + FLMR_FAST_HDR + q, 4, hipMemcpyDeviceToHost));
+    FLMR_HIP(hipMemcpy(&kc, s->cand_fast + FLMR_FAST_HDR + s->last_nqueries + q, 4, hipMemcpyDeviceToHost));
+    *state = flmr_cand_bitmaps_state(imp, word, kc, s->last_ca.n_select);
     return FLMR_OK;
 }

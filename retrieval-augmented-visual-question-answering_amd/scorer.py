@@ -414,6 +414,14 @@ class IndexScorer:
             out = out.reshape(K, -1)
         return out
 
+    def cand_bitmaps(self, query=0):
+        """What became of the candidate bitmap of `query` of the last search_batch chunk (flmr_searcher_cand_bitmaps): 0 marked in the
+        scatter pass, 1 skipped (the probed cells imply the candidates), 2 skipped and marked afterwards inside the search, -1 the batch
+        did not plan the fast list-scatter forms."""
+        st = C.c_int32(0)
+        _native.check(self._lib.flmr_searcher_cand_bitmaps(self._tap_from or self._searcher, query, C.byref(st)))
+        return int(st.value)
+
     # ---- reference-shaped API (index_storage.py:67-182) -----------------------------------------------------
     def retrieve(self, config, Q):
         """-> (candidate pids int32 ascending, centroid_scores f32 [K, nq_cand]) for ONE query (index_storage.py:67-80)."""
