@@ -145,9 +145,14 @@ def test_cfg5_one_shard_view_nbits8(hip):
     _check(hip, corpus, 32, {100: 8, 500: 2}, ks=(100, 500), max_batch=8, local_queries=True)
 
 
-def _exact_protocol_on_one_device(torch, ops, shards, Q, k, ncells, thr, ndocs, split_stage0=True, truncate=True, fallback=False):
+def _exact_protocol_on_one_device(torch, ops, shards, Q, k, ncells, thr, ndocs, split_stage0=True, truncate=True, fallback=False,
+                                  q_lens=None, after_phase1=None, report=None):
     """All ranks' phases of ShardedSearcher.search_batch_exact run in sequence on ONE device: the all-gathers are
-    torch.stack / cat, the SUM all-reduces a sum over the stack (exactly the data movement of distributed.py)."""
+    torch.stack / cat, the SUM all-reduces a sum over the stack (exactly the data movement of distributed.py).
+    q_lens: the batch's ragged lengths, handed to every phase-0 / phase-1 call (phases 2 and 3 reuse phase 1's).
+    after_phase1(shards): called once every shard's phase-1 keys exist, its searcher still holding that phase's state (taps).
+    report: a dict that receives `violated` (the truncated exchange's certificate; False for the full exchange) and the global
+    lists `s1` and `s2` as the phases 2 and 3 were handed them."""
     W, B = len(shards), Q.size(0)
     if split_stage0:
         per = -(-B // W)
@@ -157,12 +162,15 @@ def _exact_protocol_on_one_device(torch, ops, shards, Q, k, ncells, thr, ndocs, 
             iw, mc = sh.probe_dims(Q, k, ncells, thr, ndocs, 32)
             bufs = (torch.zeros((per, iw), dtype=torch.int32, device="cuda"), torch.zeros((per, mc), dtype=torch.int32, device="cuda"),
                     torch.zeros((per,), dtype=torch.int32, device="cuda"))  # what distributed.py gathers: `per` rows per rank
-            parts.append(sh.probe(Q, k, ncells, thr, ndocs, lo, min(B, lo + per) - lo, 32, out=bufs))
+            parts.append(sh.probe(Q, k, ncells, thr, ndocs, lo, min(B, lo + per) - lo, 32, q_lens=q_lens, out=bufs))
         bits, cells, ncell = (torch.cat([p_[j] for p_ in parts]) for j in range(3))
-        k1 = [sh.phase1_probed(Q, k, ncells, thr, ndocs, bits, cells, ncell, 32) for sh in shards]
+        k1 = [sh.phase1_probed(Q, k, ncells, thr, ndocs, bits, cells, ncell, 32, q_lens=q_lens) for sh in shards]
     else:
-        k1 = [sh.phase1(Q, k, ncells, thr, ndocs, 32) for sh in shards]
+        k1 = [sh.phase1(Q, k, ncells, thr, ndocs, 32, q_lens=q_lens) for sh in shards]
+    if after_phase1 is not None:
+        after_phase1(shards)
     from ravqa_amd.distributed import merge_truncated, phase1_width
+    violated = False
     m = phase1_width(ndocs, W) if truncate else ndocs
     if m < ndocs:   # each shard ships its m best keys + the certificate (distributed.py: the default exchange)
         g = torch.stack([ops.topn_keys(k_, m, ordered=False) for k_ in k1])                     # [W, B, m]
@@ -180,6 +188,8 @@ def _exact_protocol_on_one_device(torch, ops, shards, Q, k, ncells, thr, ndocs, 
     parts3 = torch.stack([sh.phase3(s2) for sh in shards])
     assert int((parts3 != 0).sum(dim=0).max()) <= 1
     fin = ops.topn_keys(parts3.sum(dim=0), min(k, ndocs // 4), ordered=True)
+    if report is not None:
+        report.update(violated=bool(violated), s1=s1, s2=s2)
     return ops.unpack_keys(fin, k)
 
 
