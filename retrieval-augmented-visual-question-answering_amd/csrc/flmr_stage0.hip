@@ -646,14 +646,16 @@ __global__ __launch_bounds__(512, 1) void s0_centroid_scores_qs(flmr_s0_args a, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// S0a, query-stationary, "hi first" (APPROX) and fp16-numerics (HI_ONLY) paths: the main loop has NO rare branch.
+// S0a, query-stationary, "hi first" (APPROX) and fp16-numerics (HI_ONLY) paths: no dense epilogue in the main loop, and the tile
+// epilogue software-pipelined under the next tile's MFMAs (the comment above the loop).
 // s0_centroid_scores_qs<.., APPROX> above tests every (tile, query) and runs the dense epilogue -- lo products, staging, row
 // stores -- inline; that keeps the queries' lo images (64 VGPRs) resident for a branch taken by < 1 % of the tiles, leaves
 // one register set for the A fragments, and -- the workgroup's eight waves being phase-locked by the block barrier -- makes
 // every tile an LDS phase (all waves fetch their fragments: 64 KB at 128 B/clk) FOLLOWED by an MFMA phase: the matrix pipe
-// measured 40 % busy.  Here a flagged (tile, query) only appends its index to a per-wave list; the main loop holds the hi
-// images and TWO fragment sets -- every tile's fragments are requested while the MFMAs of the tile before it run (the first
-// tile of the next step during this one: the barrier of step P certifies super-block P + 1) -- and nothing else; it also
+// measured 40 % busy.  Here a flagged (tile, query) only decides its idx word from the hi products or appends its index to a
+// per-wave list; the main loop holds the hi images, TWO fragment sets -- every tile's fragments are requested while the MFMAs of
+// the tile before it run (the first tiles of the next step during this one: the barrier of step P certifies super-block P + 1)
+// -- and TWO accumulator sets, so that a tile's maxima, ballots and stores issue between the MFMAs of the next tile; it also
 // leaves one column maximum per S0Q2_GRP blocks for the cell selection.  After the loop every wave works through its own list without any block
 // barrier: the queries' lo images are loaded then (the fragment registers are free), the tile's rows come straight from the
 // table into fragment layout, both products are recomputed with the same MFMA sequences -- the same bits -- and the dense
@@ -665,7 +667,8 @@ __global__ __launch_bounds__(512, 1) void s0_centroid_scores_qs(flmr_s0_args a, 
 // ------------------------------------------------------------------------------------------------
 #define S0Q2_MAX_SLICE_ROWS 8192
 #ifndef S0Q2_WAVES
-#define S0Q2_WAVES 8    // (12 -- three waves per SIMD, 24 queries per workgroup -- measured slower: the waves that do not move tiles wait for the movers)
+#define S0Q2_WAVES 8    // (12 -- three waves per SIMD, 24 queries per workgroup -- measured slower: the waves that do not move tiles wait for the movers;
+                        // 4 waves of 4 queries -- one per SIMD, operands in AGPRs -- measured no faster: DESIGN.md 4.2)
 #endif
 #ifdef S0Q_PROFILE   // development only: s_memtime clocks of wave 0 of every workgroup per phase, printed by the launcher
 __device__ unsigned long long s0q_prof[8];
@@ -750,51 +753,113 @@ __global__ __launch_bounds__(64 * S0Q2_WAVES, 1) void s0_centroid_scores_qs2(flm
         colmask[q] = full_cols[q] ? ~0ull : (((1ull << n) - 1ull) * 0x100000001ull);
         qemax[q] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(flmr_half_wave_max(i < n ? qe[q] : 0.0f))));
     }
-    auto tile_max = [](const f32x16& v) {   // one chain (v_max3): a tree makes the compiler canonicalise every raw MFMA output
-        float m = fmaxf(v[0], v[1]);
-#pragma unroll
-        for (int r = 2; r < 16; r += 2) m = fmaxf(fmaxf(m, v[r]), v[r + 1]);
-        return m;
-    };
     uint32_t aoff[8];
 #pragma unroll
     for (int s = 0; s < 8; s++) aoff[s] = (uint32_t)(i * 256 + (((8 * h + s) ^ (i & 15)) << 4));
     int nflag = 0;   // wave-uniform
     S0Q_STAMP(0);
 
-    // Software pipeline over the tiles: the fragments of a tile are fetched while the MFMAs of the tile before it run (the first
-    // tile of super-block P + 1 during step P) -- otherwise the eight waves, phase-locked by the barrier, all fetch (64 KB at
-    // 128 B/clk) and then all multiply.  For that the barrier of step P certifies super-block P + 1.
-    // VMEM order of a moving wave: prologue D0 D1 D2 (S0Q2_SBT operations each); step P: D(P+3), then one block-maximum store per
-    // query and 64-row block.  Own pieces of super-block P + 1 (the first operations of step P - 2): younger are that step's
-    // stores and one full step.
+    // Software pipeline over the tiles, two levels deep.
+    // (1) The fragments of a tile are fetched while the MFMAs of the tile before it run (the first two tiles of super-block
+    // P + 1 during step P) -- otherwise the eight waves, phase-locked by the barrier, all fetch (64 KB at 128 B/clk) and then all
+    // multiply.  For that the barrier of step P certifies super-block P + 1.
+    // (2) The epilogue of a tile -- the v_max3 chains over its accumulators, the  tmax + qe >= thr  ballots, the fold into the
+    // block and group maxima and, after the second tile of a 64-row block, the block-maximum stores -- is issued BETWEEN the
+    // MFMAs of the tile after it: a wave keeps two accumulator sets (X: even tiles, Y: odd tiles), and a segment is
+    //     8 x { <= 4 VALU of tile t - 1's epilogue | MFMA q0, MFMA q1 of tile t | ds_read_b128 of tile t + 1 }
+    // fenced slot by slot with sched_barrier (blocked MFMA and VALU sequences add up, two VALU per MFMA are free when
+    // interleaved: profiles/microbench/issue_probe.hip).  No max chain waits for its MFMA chain to drain: by its first read two
+    // MFMAs of the next tile have been issued behind the one it depends on.
+    // The rare branch comes once per tile, AFTER the segment: the OR of the tile's two flag ballots.  At that point the MFMAs of
+    // tile t have all been issued and the accumulators of tile t - 1 are still live in the other set (two sets keep exactly two
+    // tiles live, which is why the branch cannot wait for a whole 64-row block: its first tile's set is the target of the next
+    // block's first tile), so the cold path decides the idx word from them or appends to the list as before, while the matrix
+    // pipe works through tile t.
+    // A step is therefore rotated by one tile: the MFMAs of its first tile were issued at the end of the step before (in the
+    // prologue for step 0) -- its fragments come from a super-block that step's barrier certified -- and a step ends with the
+    // MFMAs of the next step's first tile, under which its own last epilogue and stores run.  The last step ends with the bare
+    // epilogue instead.
+    // VMEM order of a moving wave (unchanged by the rotation: every epilogue of step P, stores included, is issued before step
+    // P + 1's wait and dma_block): prologue D0 D1 D2 (S0Q2_SBT operations each); step P: D(P+3), then one block-maximum store
+    // per query and 64-row block (ST in all; then, every fourth step, the group maxima; flagged tiles' idx words anywhere after
+    // D(P+3)).  Own pieces of super-block P + 1 (the first operations of step P - 2): younger are that step's stores and one
+    // full step: vmcnt(SBT + 2 ST); in steps 0 and 1 (pieces from the prologue, fewer stores behind them) SBT and SBT + ST.
+    // Uncounted stores only make a wait stricter.
     constexpr int ST = S0Q2_SBT / 2 * S0Q_QT;   // stores of a step
     f16x8 avA[8], avB[8];
-    if (mover) s0q_wait_vm<S0Q2_SBT * (S0Q2_AHEAD - 1)>();   // D0
-    __syncthreads();
+    f32x16 accX[S0Q_QT], accY[S0Q_QT];
+    // the coarse level: one column maximum per S0Q2_GRP blocks (s0_select_cells reads these 32 KB per query first, and block maxima
+    // of the best groups only), when the launcher cut the slices on group boundaries
+    const bool groups = a.grp_blocks == S0Q2_GRP;
+    float gmax[S0Q_QT], cmax[S0Q_QT];   // column maxima of the running group / 64-row block
+    unsigned long long flag[S0Q_QT];    // (wave-uniform) the columns of the tile just reduced that reach the threshold
 #pragma unroll
-    for (int s = 0; s < 8; s++) avA[s] = *reinterpret_cast<const f16x8*>(abuf + aoff[s]);
-    auto tile = [&](const f16x8 (&av)[8], int t, float (&cmax)[S0Q_QT]) {   // MFMAs + maxima + flags of tile t (of the slice)
-        f32x16 acc[S0Q_QT];
+    for (int q = 0; q < S0Q_QT; q++) { gmax[q] = FLMR_NEG_INF; cmax[q] = FLMR_NEG_INF; flag[q] = 0ull; }
+    auto fetch = [&](f16x8 (&av)[8], int buf_tile) {   // buf_tile = (super-block % NBUF) * SBT + tile
+        const char* const pt_ = abuf + __builtin_amdgcn_readfirstlane(buf_tile * 8192);
 #pragma unroll
-        for (int q = 0; q < S0Q_QT; q++) {
+        for (int s = 0; s < 8; s++) av[s] = *reinterpret_cast<const f16x8*>(pt_ + aoff[s]);
+    };
+    // one segment.  MM: the MFMAs of a tile (fragments av) into `an`, and the fetch of the next tile's fragments (buffer tile
+    // next_buf_tile) into avn.  EPI: the epilogue of the tile before it, whose accumulators are `ao`; END: that tile closes the
+    // 64-row block `blk` (of the table).  Leaves flag[] of the epilogue's tile.
+    auto seg = [&](auto mm_c, auto epi_c, auto end_c, const f16x8 (&av)[8], f16x8 (&avn)[8], int next_buf_tile, f32x16 (&an)[S0Q_QT],
+                   const f32x16 (&ao)[S0Q_QT], int blk) {
+        constexpr bool MM = decltype(mm_c)::value, EPI = decltype(epi_c)::value, END = decltype(end_c)::value;
+        const char* const pn = abuf + __builtin_amdgcn_readfirstlane(next_buf_tile * 8192);
+        float m[S0Q_QT];
 #pragma unroll
-            for (int r = 0; r < 16; r++) acc[q][r] = 0.0f;
+        for (int s = 0; s < 8; s++) {
+            if constexpr (EPI) {
+                if (s >= 1 && s <= 2 * S0Q_QT) {   // slots 1, 2: query 0, slots 3, 4: query 1 (ONE v_max3 chain each: a tree makes the compiler canonicalise every raw MFMA output)
+                    const int q = (s - 1) / 2;
+                    if ((s - 1) % 2 == 0) {
+                        m[q] = fmaxf(ao[q][0], ao[q][1]);
 #pragma unroll
-            for (int s = 0; s < 8; s++) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[s], bh[q][s], acc[q], 0, 0, 0);
+                        for (int r = 2; r < 8; r += 2) m[q] = fmaxf(fmaxf(m[q], ao[q][r]), ao[q][r + 1]);
+                    } else {
+#pragma unroll
+                        for (int r = 8; r < 16; r += 2) m[q] = fmaxf(fmaxf(m[q], ao[q][r]), ao[q][r + 1]);
+                        cmax[q] = fmaxf(END ? cmax[q] : FLMR_NEG_INF, m[q]);
+                        flag[q] = __ballot(m[q] + qe[q] >= a.thr) & colmask[q];
+                    }
+                }
+                if (END && s > 2 * S0Q_QT && s <= 3 * S0Q_QT) {   // slots 5, 6: the 64-row block's column maxima, for the cell selection
+                    const int q = s - 2 * S0Q_QT - 1;
+                    const float mb = flmr_xhalf_max(cmax[q]);
+                    gmax[q] = fmaxf(gmax[q], mb);
+                    if (lane < 32) a.part_val[((size_t)bq[q] * a.nblk + blk) * a.ncol + i] = (i < nqc[q]) ? mb : FLMR_NEG_INF;
+                }
+            }
+            if constexpr (MM) {
+#pragma unroll
+                for (int q = 0; q < S0Q_QT; q++) {
+                    f32x16 c;
+                    if (s == 0) {
+#pragma unroll
+                        for (int r = 0; r < 16; r++) c[r] = 0.0f;
+                    } else {
+                        c = an[q];
+                    }
+                    an[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[s], bh[q][s], c, 0, 0, 0);
+                }
+                avn[s] = *reinterpret_cast<const f16x8*>(pn + aoff[s]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
+    };
+    // the cold path of tile t (of the slice), accumulators acc, flagged by seg.
+    // Wave-uniform and rare on a corpus whose queries meet few centroids (1 % of the tiles at the policy thresholds of the
+    // synthetic corpus; MOST tiles once thousands of centroids pass the threshold): some row of this tile survives (or,
+    // with the lo products still missing, may survive).  The tile's idx word -- one bit per row: does the row's maximum
+    // over the query's columns reach the threshold -- is decided HERE from the hi products whenever no row's maximum lies
+    // within the bound of the threshold: a transpose-reduce leaves row (i >> 1)'s maximum over the 32 columns in lane i
+    // (16 cross-lane exchanges for the 16 x 32 values of a half-wave, not 16 x 5), a ballot collects the bits.  Only a
+    // tile with an ambiguous row goes on the list of the deferred pass (both products, dense epilogue).
+    auto cold = [&](const f32x16 (&acc)[S0Q_QT], int t) {
 #pragma unroll
         for (int q = 0; q < S0Q_QT; q++) {
-            const float tmax = tile_max(acc[q]);
-            cmax[q] = fmaxf(cmax[q], tmax);
-            // wave-uniform and rare on a corpus whose queries meet few centroids (1 % of the tiles at the policy thresholds of the
-            // synthetic corpus; MOST tiles once thousands of centroids pass the threshold): some row of this tile survives (or,
-            // with the lo products still missing, may survive).  The tile's idx word -- one bit per row: does the row's maximum
-            // over the query's columns reach the threshold -- is decided HERE from the hi products whenever no row's maximum lies
-            // within the bound of the threshold: a transpose-reduce leaves row (i >> 1)'s maximum over the 32 columns in lane i
-            // (16 cross-lane exchanges for the 16 x 32 values of a half-wave, not 16 x 5), a ballot collects the bits.  Only a
-            // tile with an ambiguous row goes on the list of the deferred pass (both products, dense epilogue).
-            if ((__ballot(tmax + qe[q] >= a.thr) & colmask[q]) != 0ull) {
+            if (flag[q] != 0ull) {
 #ifdef S0Q2_NO_INLINE_IDX   // development A/B: every flagged tile goes to the deferred pass (the form before round 4)
                 if (lane == 0) flist[nflag] = (uint16_t)(t * S0Q_QT + q);
                 nflag++;
@@ -838,17 +903,18 @@ __global__ __launch_bounds__(64 * S0Q2_WAVES, 1) void s0_centroid_scores_qs2(flm
             }
         }
     };
-    auto fetch = [&](f16x8 (&av)[8], int buf_tile) {   // buf_tile = (super-block % NBUF) * SBT + tile
-        const char* const pt_ = abuf + __builtin_amdgcn_readfirstlane(buf_tile * 8192);
+    auto any_flag = [&]() {
+        unsigned long long f = 0ull;
 #pragma unroll
-        for (int s = 0; s < 8; s++) av[s] = *reinterpret_cast<const f16x8*>(pt_ + aoff[s]);
+        for (int q = 0; q < S0Q_QT; q++) f |= flag[q];
+        return __builtin_expect(f != 0ull, 0);
     };
-    // the coarse level: one column maximum per S0Q2_GRP blocks (s0_select_cells reads these 32 KB per query first, and block maxima
-    // of the best groups only), when the launcher cut the slices on group boundaries
-    const bool groups = a.grp_blocks == S0Q2_GRP;
-    float gmax[S0Q_QT];
-#pragma unroll
-    for (int q = 0; q < S0Q_QT; q++) gmax[q] = FLMR_NEG_INF;
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (mover) s0q_wait_vm<S0Q2_SBT * (S0Q2_AHEAD - 1)>();   // D0
+    __syncthreads();
+    fetch(avA, 0);
+    seg(yes, no, no, avA, avB, 1, accX, accY, 0);   // tile 0 of the slice
     for (int p = 0; p < nblocks; p++) {
         if (mover) {
             if (p == 0) s0q_wait_vm<S0Q2_SBT>(); else if (p == 1) s0q_wait_vm<S0Q2_SBT + ST>(); else s0q_wait_vm<S0Q2_SBT + 2 * ST>();
@@ -860,21 +926,16 @@ __global__ __launch_bounds__(64 * S0Q2_WAVES, 1) void s0_centroid_scores_qs2(flm
         dma_block(p + S0Q2_AHEAD);
         const int bt = (p % S0Q2_NBUF) * S0Q2_SBT, bn = ((p + 1) % S0Q2_NBUF) * S0Q2_SBT;
 #pragma unroll
-        for (int u2 = 0; u2 < S0Q2_SBT / 2; u2++) {   // one 64-row block: tiles 2 u2 (in A) and 2 u2 + 1 (B)
-            fetch(avB, bt + 2 * u2 + 1);
-            float cmax[S0Q_QT];
-#pragma unroll
-            for (int q = 0; q < S0Q_QT; q++) cmax[q] = FLMR_NEG_INF;
-            tile(avA, S0Q2_SBT * p + 2 * u2, cmax);
-            fetch(avA, 2 * u2 + 2 < S0Q2_SBT ? bt + 2 * u2 + 2 : bn);   // (the last one: first tile of the next super-block)
-            tile(avB, S0Q2_SBT * p + 2 * u2 + 1, cmax);
-#pragma unroll
-            for (int q = 0; q < S0Q_QT; q++) {   // the 64-row block's column maxima, for the cell selection
-                const float m = flmr_xhalf_max(cmax[q]);
-                gmax[q] = fmaxf(gmax[q], m);
-                if (lane < 32)
-                    a.part_val[((size_t)bq[q] * a.nblk + ((row_begin + 32 * S0Q2_SBT * p + 64 * u2) >> 6)) * a.ncol + i] = (i < nqc[q]) ? m : FLMR_NEG_INF;
-            }
+        for (int u2 = 0; u2 < S0Q2_SBT / 2; u2++) {   // one 64-row block: tiles 2 u2 (accumulated in X) and 2 u2 + 1 (Y)
+            const int t0 = S0Q2_SBT * p + 2 * u2, blk = (row_begin + 32 * t0) >> 6;
+            // MFMAs of tile 2 u2 + 1, fragments of 2 u2 + 2 (past the step: of the next super-block), epilogue of 2 u2
+            seg(yes, yes, no, avB, avA, 2 * u2 + 2 < S0Q2_SBT ? bt + 2 * u2 + 2 : bn, accY, accX, blk);
+            if (any_flag()) cold(accX, t0);
+            // MFMAs of tile 2 u2 + 2, fragments of 2 u2 + 3, epilogue of 2 u2 + 1 and of the block
+            const int nb = 2 * u2 + 3 < S0Q2_SBT ? bt + 2 * u2 + 3 : bn + 2 * u2 + 3 - S0Q2_SBT;
+            if (2 * u2 + 2 < S0Q2_SBT || p + 1 < nblocks) seg(yes, yes, yes, avA, avB, nb, accX, accY, blk);
+            else seg(no, yes, yes, avA, avB, nb, accX, accY, blk);   // (the slice's last tile: nothing follows it)
+            if (any_flag()) cold(accY, t0 + 1);
         }
         if (groups && (p + 1) % (S0Q2_GRP * 2 / S0Q2_SBT) == 0) {   // (wave-uniform) a group of S0Q2_GRP blocks is complete
             const int g = (row_begin + 32 * S0Q2_SBT * p) / (64 * S0Q2_GRP);
