@@ -51,11 +51,11 @@ int main(int argc, char** argv) {
     {
         int nb = 0;
 #ifdef X2_ROWS_IN_REGS
-        const size_t lds = (size_t)X2_WAVES * X2R_WAVE_LDS;
+        const size_t lds = x2r_lds{}.bytes;
         printf("rows in registers: %d tiles in flight per wave, launch bound %d waves per SIMD\n", X2_ROWS_IN_REGS, X2_REG_MINW);
         CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, filter_stage2_xreg_kernel<true>, 64 * X2_WAVES, lds));
 #else
-        const size_t lds = (size_t)X2_WAVES * X2_WAVE_LDS;
+        const size_t lds = x2_lds{}.bytes;
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(filter_stage2_xcd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, filter_stage2_xcd_kernel<false>, 64 * X2_WAVES, lds));
 #endif

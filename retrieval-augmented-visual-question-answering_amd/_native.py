@@ -13,7 +13,7 @@ REPO_ROOT = os.path.dirname(PKG_DIR)
 LIB_PATH = os.environ.get("FLMR_HIP_LIB") or os.path.join(PKG_DIR, "lib", "libflmr_hip.so")  # override: A/B-ing kernel builds
 CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["flmr_index.hip", "flmr_stage0.hip", "flmr_candidates.hip", "flmr_filter.hip", "flmr_stage1_dense.hip", "flmr_stage2_walk.hip", "flmr_stage2_xcd.hip", "flmr_maxsim.hip", "flmr_search.hip", "flmr_ops.hip", "flmr_build.hip", "flmr_build_f16.hip", "flmr_ivf.hip", "flmr_collective.hip", "flmr_score_grad.hip", "flmr_rescore.hip", "flmr_score_half.hip", "flmr_rag_loss.hip"]
-HEADERS = ["flmr_common.h", "flmr_device.h", "flmr_maxsim_tile.h"]
+HEADERS = ["flmr_common.h", "flmr_device.h", "flmr_lds.h", "flmr_maxsim_tile.h"]
 
 FLMR_MEM_HOST, FLMR_MEM_DEVICE = 0, 1
 FLMR_BF16 = 2              # (with the two below) the logits dtype of flmr_rag_token_ll_fwd / _bwd

@@ -471,17 +471,33 @@ __global__ __launch_bounds__(256) void cand_deferred_bitmaps_kernel(flmr_cand_ar
 // requested a whole chunk ahead.
 // F16: FLMR_NUMERICS_GPU_FP16 (column maxima and sums rounded to fp16, flmr_device.h); a template parameter so that the
 // default instantiation carries none of it (as a kernel argument the selects cost this register-bound kernel 0.8 ms per step)
+struct s1s_lds {
+    flmr_lds c;
+    size_t cb = c.take<uint32_t>(CAND_CHUNK_WORDS);                     // candidate bitmap of the chunk
+    size_t hb = c.take<uint32_t>(CAND_CHUNK_WORDS);                     // hit-set bitmap
+    size_t cbase = c.take<uint16_t>(CAND_CHUNK_WORDS);                  // exclusive candidate count before word w
+    size_t hbase = c.take<uint16_t>(CAND_CHUNK_WORDS);                  // exclusive (candidate & hit) count before word w
+    size_t acc = c.take<int>(S1S_SLOTS * S1S_STRIDE + 96);              // [S1S_SLOTS][S1S_STRIDE] (+ 96 scratch words of slot-less lanes)
+    size_t rsum = c.take<float>(1024);                                  // [1024] stage-1 score of a passage whose only surviving centroid is list j
+    size_t queue = c.take<int>(S1S_QCAP);                               // [S1S_QCAP] slot << S1S_IDBITS | list
+    size_t qpid = c.take<uint16_t>(S1S_QCAP);                           // [S1S_QCAP] the queued pair's passage (inside the chunk)
+    size_t bytes = c.bytes;
+};
+static_assert(s1s_lds{}.bytes == 163456, "slot kernel's dynamic LDS");
+static_assert(s1s_lds{}.bytes + sizeof(int) * (S1S_WAVES + 2) /* static: scan_lds, s_base, s_qn */ <= FLMR_LDS_CU_BYTES, "cand_mark_score_kernel fills the CU's LDS: one workgroup per CU");
+
 template <bool F16>
 __global__ __launch_bounds__(64 * S1S_WAVES) void cand_mark_score_kernel(flmr_cand_args a, int cpb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t* cb = reinterpret_cast<uint32_t*>(smem);                   // candidate bitmap of the chunk
-    uint32_t* hb = cb + CAND_CHUNK_WORDS;                               // hit-set bitmap
-    uint16_t* cbase = reinterpret_cast<uint16_t*>(hb + CAND_CHUNK_WORDS);  // exclusive candidate count before word w
-    uint16_t* hbase = cbase + CAND_CHUNK_WORDS;                         // exclusive (candidate & hit) count before word w
-    int* acc = reinterpret_cast<int*>(hbase + CAND_CHUNK_WORDS);        // [S1S_SLOTS][S1S_STRIDE] (+ 96 scratch words)
-    float* rsum = reinterpret_cast<float*>(acc + S1S_SLOTS * S1S_STRIDE + 96);   // [1024] stage-1 score of a passage whose only surviving centroid is list j
-    int* queue = reinterpret_cast<int*>(rsum + 1024);                  // [S1S_QCAP] slot << S1S_IDBITS | list
-    uint16_t* qpid = reinterpret_cast<uint16_t*>(queue + S1S_QCAP);    // [S1S_QCAP] the queued pair's passage (inside the chunk)
+    constexpr s1s_lds L;
+    uint32_t* cb = reinterpret_cast<uint32_t*>(smem + L.cb);
+    uint32_t* hb = reinterpret_cast<uint32_t*>(smem + L.hb);
+    uint16_t* cbase = reinterpret_cast<uint16_t*>(smem + L.cbase);
+    uint16_t* hbase = reinterpret_cast<uint16_t*>(smem + L.hbase);
+    int* acc = reinterpret_cast<int*>(smem + L.acc);
+    float* rsum = reinterpret_cast<float*>(smem + L.rsum);
+    int* queue = reinterpret_cast<int*>(smem + L.queue);
+    uint16_t* qpid = reinterpret_cast<uint16_t*>(smem + L.qpid);
     __shared__ int scan_lds[S1S_WAVES];
     __shared__ int s_base, s_qn;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -881,7 +897,7 @@ __global__ __launch_bounds__(64 * S1S_WAVES) void cand_mark_score_kernel(flmr_ca
 //            arithmetic, bit for bit) and writes the key at the END of the chunk's range.
 // Bitmaps, queue and counters rotate over three sets and the key buffer over two, so that a wave may run ahead into the next
 // chunk's marking while others still read this chunk's: each set is cleared / reset in the period after its last reader.
-// Eight waves and 77 KB of LDS: two workgroups per CU hide each other's barrier and LDS round trips.
+// Eight waves and 73 KB of LDS: two workgroups per CU hide each other's barrier and LDS round trips.
 // What it does not handle it hands over whole, per query (fast_state[FLMR_FAST_HDR + b] != 0 -> the later kernels redo the query): more
 // staged keys or queued pairs than fit (a corpus whose clusters overlap: the slot kernel's dense form), more than 512 lists.
 // Two cumulative counters (queries handed over after trying / tried) switch a searcher whose queries mostly overflow to trying
@@ -931,14 +947,27 @@ __device__ unsigned long long cf_prof[12];
 // workgroup runs one).  Every pair of a surviving list is then a candidate's, and the body leaves out what only the candidate bitmap
 // needs: the probed cells' slices (mc, raw_c and their chunk-table reads), the marks and reads of `cb` and its clearing, the
 // cand_bits and chunk_cnt stores; the chunk's hit count is popc(hb).  Nothing is added: same barriers, same waits, the same keys.
+struct cf_lds {
+    flmr_lds c;
+    size_t bm = c.take<uint32_t>(9 * CAND_CHUNK_WORDS);   // [3][candidate | hit | several][CAND_CHUNK_WORDS]
+    size_t kbuf = c.take<uint32_t>(2 * CF_KCAP);          // [2][CF_KCAP] list << 15 | passage inside the chunk
+    size_t queue = c.take<uint32_t>(3 * CF_QCAP);         // [3][CF_QCAP] passage (inside the chunk) | list << 16
+    size_t rows = c.take<int>(CF_RC * 32);                // [CF_RC][32] score rows of the query's first surviving lists (order-encoded, floored)
+    size_t rtab = c.take<uint32_t>(CF_MAXLISTS);          // [CF_MAXLISTS] score half of the key of a passage whose only surviving centroid is list j
+    size_t bytes = c.bytes;
+};
+static_assert(cf_lds{}.bytes == 74752, "queue form's dynamic LDS");
+static_assert(2 * (cf_lds{}.bytes + 3 * sizeof(cf_chunk_state) + 4 * sizeof(int) /* static: st, s_tot, s_arr, s_abort */) <= FLMR_LDS_CU_BYTES, "cand_fast_kernel: two workgroups per CU");
+
 template <bool F16, bool IMP>
 __device__ __forceinline__ void cand_fast_body(const flmr_cand_args& a, int cpb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t* bm = reinterpret_cast<uint32_t*>(smem);                          // [3][candidate | hit | several][CAND_CHUNK_WORDS]
-    uint32_t* kbuf = bm + 9 * CAND_CHUNK_WORDS;                                // [2][CF_KCAP] list << 15 | passage inside the chunk
-    uint32_t* queue = kbuf + 2 * CF_KCAP;                                      // [3][CF_QCAP] passage (inside the chunk) | list << 16
-    int* rows = reinterpret_cast<int*>(queue + 3 * CF_QCAP);                   // [CF_RC][32] score rows of the query's first surviving lists (order-encoded, floored)
-    uint32_t* rtab = reinterpret_cast<uint32_t*>(rows + CF_RC * 32);           // [CF_MAXLISTS] score half of the key of a passage whose only surviving centroid is list j
+    constexpr cf_lds L;
+    uint32_t* bm = reinterpret_cast<uint32_t*>(smem + L.bm);
+    uint32_t* kbuf = reinterpret_cast<uint32_t*>(smem + L.kbuf);
+    uint32_t* queue = reinterpret_cast<uint32_t*>(smem + L.queue);
+    int* rows = reinterpret_cast<int*>(smem + L.rows);
+    uint32_t* rtab = reinterpret_cast<uint32_t*>(smem + L.rtab);
     __shared__ cf_chunk_state st[3];
     __shared__ int s_tot, s_arr, s_abort[2];   // s_abort[round & 1]: set during a round, read after the NEXT round's barrier
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, k = lane & 31;
@@ -1351,14 +1380,27 @@ static_assert(CF_DSLOTS == CF_DSLOTS_LIMIT, "cand_plan_kernel plans against this
 #define CF_DRC 128         // surviving lists whose score rows are kept in LDS
 #define CF_DFQ 16          // surviving lists per wave kept in registers from the marking to the pair pass
 
+struct cfd_lds {
+    flmr_lds c;
+    size_t bm = c.take<uint32_t>(4 * CAND_CHUNK_WORDS);         // [2][candidate | hit][CAND_CHUNK_WORDS]
+    size_t acc = c.take<int>(CF_DSLOTS * S1S_STRIDE + 64);      // [CF_DSLOTS][33] column maxima (+ 64 scratch words)
+    size_t rows = c.take<int>(CF_DRC * 32);                     // [CF_DRC][32]
+    size_t wslot = c.take<uint16_t>(CAND_CHUNK_WORDS);          // [CAND_CHUNK_WORDS] slot of a word's first hit candidate
+    size_t spid = c.take<uint16_t>(CF_DSLOTS);                  // [CF_DSLOTS] the slot's passage (inside the chunk)
+    size_t bytes = c.bytes;
+};
+static_assert(cfd_lds{}.bytes == 69376, "small-dense form's dynamic LDS");
+static_assert(2 * (cfd_lds{}.bytes + sizeof(int) * (CF_WAVES * 66 + 6) /* static: vs_all and six words */) <= FLMR_LDS_CU_BYTES, "cand_dense_small_kernel: two workgroups per CU");
+
 template <bool F16>
 __global__ __launch_bounds__(CF_THREADS, 2) void cand_dense_small_kernel(flmr_cand_args a, int cpb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t* bm = reinterpret_cast<uint32_t*>(smem);                          // [2][candidate | hit][CAND_CHUNK_WORDS]
-    int* acc = reinterpret_cast<int*>(bm + 4 * CAND_CHUNK_WORDS);              // [CF_DSLOTS][33] column maxima (+ 64 scratch words)
-    int* rows = acc + CF_DSLOTS * S1S_STRIDE + 64;                             // [CF_DRC][32]
-    uint16_t* wslot = reinterpret_cast<uint16_t*>(rows + CF_DRC * 32);         // [CAND_CHUNK_WORDS] slot of a word's first hit candidate
-    uint16_t* spid = wslot + CAND_CHUNK_WORDS;                                 // [CF_DSLOTS] the slot's passage (inside the chunk)
+    constexpr cfd_lds L;
+    uint32_t* bm = reinterpret_cast<uint32_t*>(smem + L.bm);
+    int* acc = reinterpret_cast<int*>(smem + L.acc);
+    int* rows = reinterpret_cast<int*>(smem + L.rows);
+    uint16_t* wslot = reinterpret_cast<uint16_t*>(smem + L.wslot);
+    uint16_t* spid = reinterpret_cast<uint16_t*>(smem + L.spid);
     __shared__ int s_tot, s_arr, s_slots, s_nh, s_base, s_abort;
     __shared__ __attribute__((aligned(8))) int vs_all[CF_WAVES][66];           // a list's slots, packed, per wave (see the pair pass)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, k = lane & 31;
@@ -1722,8 +1764,7 @@ int flmr_launch_candidates_chunked(const flmr_cand_args& a, hipStream_t st) {
                        a.scatter ? 8 : 2, a.idx_prefix, a.rows_out, a.cen16, a.q_hi, a.q_lo, a.row_ovf, a.scatter ? a.fast_state : nullptr,
                        (a.scatter && a.fast_state && a.s1d_mode) ? a.s1d_any : nullptr);
     if (a.scatter) {
-        const size_t lds = (size_t)CAND_CHUNK_WORDS * (2 * sizeof(uint32_t) + 2 * sizeof(uint16_t)) +
-                           ((size_t)S1S_SLOTS * S1S_STRIDE + 96 + 1024 + S1S_QCAP) * sizeof(int) + S1S_QCAP * sizeof(uint16_t);   // + scratch words of slot-less lanes, list constants, queue (+ its passages)
+        const size_t lds = s1s_lds{}.bytes;
         const void* kfn = a.f16_round ? reinterpret_cast<const void*>(cand_mark_score_kernel<true>) : reinterpret_cast<const void*>(cand_mark_score_kernel<false>);
         FLMR_HIP(hipFuncSetAttribute(kfn,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1733,8 +1774,7 @@ int flmr_launch_candidates_chunked(const flmr_cand_args& a, hipStream_t st) {
         while (cpb > 1 && (int64_t)a.nqueries * ((a.nchunks + cpb - 1) / cpb) < 512) cpb >>= 1;
         if (a.fast_state) {   // the plan per query (measured on a sample of its chunks), then the queue form; what it hands over is done by the slot kernel below
             hipLaunchKernelGGL(cand_plan_kernel, dim3(a.nqueries), dim3(64 * PLAN_WAVES), 0, st, a);
-            const size_t flds = (size_t)9 * CAND_CHUNK_WORDS * sizeof(uint32_t) + (size_t)2 * CF_KCAP * sizeof(uint32_t) + (size_t)CF_MAXLISTS * sizeof(uint32_t) +
-                                (size_t)3 * CF_QCAP * sizeof(uint32_t) + (size_t)CF_RC * 32 * sizeof(int);
+            const size_t flds = cf_lds{}.bytes;
             const void* ffn = a.f16_round ? reinterpret_cast<const void*>(cand_fast_kernel<true>) : reinterpret_cast<const void*>(cand_fast_kernel<false>);
             FLMR_HIP(hipFuncSetAttribute(ffn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
             int fcpb = 8;   // two resident workgroups per CU: twice the slot kernel's workgroups
@@ -1744,8 +1784,7 @@ int flmr_launch_candidates_chunked(const flmr_cand_args& a, hipStream_t st) {
             else
                 hipLaunchKernelGGL(cand_fast_kernel<false>, dim3(a.nqueries, (a.nchunks + fcpb - 1) / fcpb), dim3(CF_THREADS), flds, st, a, fcpb);
             {   // the small-dense form: the queries planned for it
-                const size_t dlds = (size_t)4 * CAND_CHUNK_WORDS * sizeof(uint32_t) + ((size_t)CF_DSLOTS * S1S_STRIDE + 64) * sizeof(int) +
-                                    (size_t)CF_DRC * 32 * sizeof(int) + ((size_t)CAND_CHUNK_WORDS + CF_DSLOTS) * sizeof(uint16_t);
+                const size_t dlds = cfd_lds{}.bytes;
                 const void* dfn = a.f16_round ? reinterpret_cast<const void*>(cand_dense_small_kernel<true>) : reinterpret_cast<const void*>(cand_dense_small_kernel<false>);
                 FLMR_HIP(hipFuncSetAttribute(dfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
                 if (a.f16_round)

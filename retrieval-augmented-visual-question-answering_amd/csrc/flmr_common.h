@@ -78,6 +78,18 @@ int flmr_process_options(flmr_options* out);
 static inline int64_t flmr_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t flmr_round_up(int64_t a, int64_t b) { return flmr_ceil_div(a, b) * b; }
 
+// Workgroups per query (grid.y) of the kernels whose waves each take every W-th document of a query (W = waves in the grid row):
+// enough to put `target_waves` waves on the chip, but never more than 64 documents per wave -- the kernels keep a wave's documents
+// one per lane, this is the launch contract their "<= 64" comments name -- nor fewer than one document per workgroup, and >= 1.
+static inline int flmr_doc_grid(int target_waves, int waves_per_workgroup, int nqueries, int max_count) {
+    int G = (int)flmr_ceil_div(target_waves, waves_per_workgroup * (int64_t)nqueries);
+    const int gmin = (int)flmr_ceil_div(max_count, waves_per_workgroup * 64);
+    const int gmax = (int)flmr_ceil_div(max_count, waves_per_workgroup);
+    if (G < gmin) G = gmin;
+    if (G > gmax) G = gmax;
+    return G < 1 ? 1 : G;
+}
+
 // ---- the argument rules of the MaxSim entry points (padded, typed, gathered, index; forward and backward) -------------------
 // One statement of each rule, INVALID before UNSUPPORTED.  An entry point keeps only what is its own (NULL pointers, dtypes,
 // which sizes it has, where an empty batch returns) and switches a rule off by passing the value that satisfies it:

@@ -1,6 +1,7 @@
 // Device-side helpers (wave64 reductions, block scans, small sorted lists) for the gfx950 kernels.
 #pragma once
 #include "flmr_common.h"
+#include "flmr_lds.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

@@ -122,6 +122,24 @@ __device__ __forceinline__ int s1_list_hits(const int* cd, const s1_idx_view& iv
 // ------------------------------------------------------------------------------------------------
 #define S1_ITEMS_G 32   // parts per query
 
+// T column tiles; compact: 16-bit row ids in the hit lists; lds_idx: the idx mask and its prefix are staged (USE_LDS_IDX)
+struct s1_scan_lds {
+    int T, compact, nqueries, idx_words;
+    bool lds_idx;
+    flmr_lds c;   // (align 1 below: every size before is a multiple of 4, and rounding a runtime offset costs the kernel instructions)
+    int tr_wave = S1_GROUP * (T * 32 + 1);                                     // (floats)
+    size_t tr = c.take<float>(S1_WAVES * tr_wave);                             // [S1_WAVES][S1_GROUP][T * 32 + 1] transposed column maxima
+    int lists_wave = S1_PAIRS_IN_FLIGHT * 2 * S1_HITS_MAX * (compact ? sizeof(uint16_t) : sizeof(int));   // (bytes)
+    size_t lists = c.take<char>(S1_WAVES * lists_wave);                        // [S1_WAVES][S1_PAIRS_IN_FLIGHT][2][S1_HITS_MAX] hit lists, u16 (compact) or i32
+    size_t scan_list = c.take<int>(nqueries, 1);                               // the queries that are scanned
+    size_t lidx = c.take<uint32_t>(lds_idx ? idx_words : 0, 1);                // the query's idx mask
+    size_t lpre = c.take<uint16_t>(lds_idx ? idx_words : 0, 1);                // its prefix counts
+    size_t bytes = c.bytes + (lds_idx ? 16 : 0);                               // (16 spare bytes behind the prefix, as ever)
+};
+static_assert(s1_scan_lds{1, 1, 256, 0, false}.bytes == 51200 && s1_scan_lds{1, 1, 256, 4096, true}.bytes == 75792,
+              "filter_stage1_kernel's dynamic LDS: one column tile, compact rows, 256 queries; without / with the mask of K = 131072");
+static_assert(2 * (s1_scan_lds{1, 1, 256, 4096, true}.bytes + sizeof(int) * (17 + 1) /* static: scan_lds, s_nscan */) <= FLMR_LDS_CU_BYTES, "filter_stage1_kernel: two workgroups per CU at that size");
+
 template <bool USE_LDS_IDX, int TM>
 __global__ __launch_bounds__(512, 4) void filter_stage1_kernel(flmr_filter_args f, const uint32_t* idx_bits,
                                                             int32_t idx_words, const int32_t* cand,
@@ -136,15 +154,13 @@ __global__ __launch_bounds__(512, 4) void filter_stage1_kernel(flmr_filter_args 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int T = (f.nq_cand + 31) >> 5;  // column tiles of 32 (<= TM); f.ncol is the row stride of the score table
     const int ncolp = T * 32 + 1;
-    // LDS carve: [tr: S1_WAVES*S1_GROUP*ncolp f32][hit lists: S1_WAVES * PAIRS * 2 * S1_HITS_MAX u16 (compact) or i32][scan list:
-    // nqueries i32][bits][prefix u16]
-    float* tr = reinterpret_cast<float*>(smem) + (size_t)wave * S1_GROUP * ncolp;
-    char* after_tr = reinterpret_cast<char*>(reinterpret_cast<float*>(smem) + (size_t)S1_WAVES * S1_GROUP * ncolp);
+    const s1_scan_lds L{T, f.cs_compact, f.nqueries, idx_words, USE_LDS_IDX};
+    float* tr = reinterpret_cast<float*>(smem + L.tr) + wave * L.tr_wave;
     const size_t list_elem = f.cs_compact ? sizeof(uint16_t) : sizeof(int);
-    char* my_lists = after_tr + (size_t)wave * S1_PAIRS_IN_FLIGHT * 2 * S1_HITS_MAX * list_elem;
-    int* scan_list = reinterpret_cast<int*>(after_tr + (size_t)S1_WAVES * S1_PAIRS_IN_FLIGHT * 2 * S1_HITS_MAX * list_elem);
-    uint32_t* lidx = reinterpret_cast<uint32_t*>(scan_list + f.nqueries);
-    uint16_t* lpre = reinterpret_cast<uint16_t*>(lidx + idx_words);
+    char* my_lists = smem + L.lists + wave * L.lists_wave;
+    int* scan_list = reinterpret_cast<int*>(smem + L.scan_list);
+    uint32_t* lidx = reinterpret_cast<uint32_t*>(smem + L.lidx);
+    uint16_t* lpre = reinterpret_cast<uint16_t*>(smem + L.lpre);
 
     // ---- which queries are scanned at all (usually none: every workgroup leaves here) ----
     if (threadIdx.x == 0) s_nscan = 0;
@@ -415,13 +431,9 @@ int flmr_launch_filter_stage1(const flmr_filter_args& f, const uint32_t* idx_bit
                               const uint8_t* hit_flags, hipStream_t st, const int32_t* skip) {
     const int T = (f.nq_cand + 31) >> 5;
     if (T > 4) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "stage 1: nq_cand=%d > 128", f.nq_cand);
-    const size_t tr_bytes = (size_t)S1_WAVES * S1_GROUP * (T * 32 + 1) * sizeof(float);
-    const size_t list_bytes = (size_t)S1_WAVES * S1_PAIRS_IN_FLIGHT * 2 * S1_HITS_MAX * (f.cs_compact ? sizeof(uint16_t) : sizeof(int)) +
-                              (size_t)f.nqueries * sizeof(int);   // the waves' hit lists + the list of scanned queries
-    const size_t idx_bytes = (size_t)idx_words * 4 + (size_t)idx_words * 2 + 16;
-    const bool lds_idx = tr_bytes + list_bytes + idx_bytes <= 100 * 1024;  // else probe the mask (and its prefix) through L1/L2
+    const bool lds_idx = s1_scan_lds{T, f.cs_compact, f.nqueries, idx_words, true}.bytes <= 100 * 1024;  // else probe the mask (and its prefix) through L1/L2
     if (f.cs_compact && !lds_idx && !f.idx_prefix) FLMR_FAIL(FLMR_ERR_INVALID, "compact score rows need the idx prefix");
-    const size_t lds = tr_bytes + list_bytes + (lds_idx ? idx_bytes : 0);
+    const size_t lds = s1_scan_lds{T, f.cs_compact, f.nqueries, idx_words, lds_idx}.bytes;
     const void* fn = lds_idx ? (T == 1 ? reinterpret_cast<const void*>(filter_stage1_kernel<true, 1>) : reinterpret_cast<const void*>(filter_stage1_kernel<true, 4>))
                              : (T == 1 ? reinterpret_cast<const void*>(filter_stage1_kernel<false, 1>) : reinterpret_cast<const void*>(filter_stage1_kernel<false, 4>));
     if (lds > 48 * 1024) FLMR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -444,6 +456,15 @@ int flmr_launch_filter_stage1(const flmr_filter_args& f, const uint32_t* idx_bit
 // Stage 2: every centroid counts (idx == all ones).  One wave per surviving doc; each half-wave gathers
 // one 128-byte score row per step, 4 steps in flight.  grid = (nqueries, ceil(max_count / 4)), block 256.
 // ------------------------------------------------------------------------------------------------
+struct s2_gather_lds {
+    int T;   // column tiles
+    flmr_lds c;
+    size_t tr_wave = T * 32 + 1;                         // (floats)
+    size_t tr = c.take<float>(S2_WAVES * tr_wave);       // [S2_WAVES][T * 32 + 1] a document's column maxima
+    size_t bytes = c.bytes;
+};
+static_assert(s2_gather_lds{1}.bytes == 528, "filter_stage2_kernel's dynamic LDS at one column tile");
+
 __global__ __launch_bounds__(256) void filter_stage2_kernel(flmr_filter_args f, const int32_t* pids, int64_t pid_stride,
                                                             const int32_t* counts, uint64_t* keys,
                                                             int64_t key_stride) {
@@ -455,8 +476,8 @@ __global__ __launch_bounds__(256) void filter_stage2_kernel(flmr_filter_args f, 
     const int qlen = f.q_lens ? f.q_lens[b] : f.nq_cand;
     const int nqc = qlen < f.nq_cand ? qlen : f.nq_cand;
     const int T = (f.nq_cand + 31) >> 5;
-    const int ncolp = T * 32 + 1;
-    float* tr = reinterpret_cast<float*>(smem) + (size_t)wave * ncolp;
+    const s2_gather_lds L{T};
+    float* tr = reinterpret_cast<float*>(smem + L.tr) + wave * L.tr_wave;
     if (d >= n) return;  // no block-level barrier below
     const float* cs = f.cs + (size_t)b * f.cs_query_stride;
     const int pid = pids[(size_t)b * pid_stride + d];
@@ -510,6 +531,23 @@ __global__ __launch_bounds__(256) void filter_stage2_kernel(flmr_filter_args f, 
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 s2h8 __attribute__((ext_vector_type(8)));
 
+// the recompute kernels: filter_stage2_mfma_kernel <4, false, false> (register gathers: the column maxima alone),
+// filter_stage2_lds_kernel<WAVES, B_LDS> <WAVES, true, B_LDS>
+template <int WAVES, bool ROWBUF, bool B_LDS>
+struct s2_mfma_lds {
+    flmr_lds c;
+    size_t tr_wave = 33;                                                 // (floats)
+    size_t tr = c.take<float>(WAVES * tr_wave);                          // [WAVES][33] a document's column maxima
+    size_t rowbuf_wave = 32 * FLMR_DIM * sizeof(_Float16);               // a tile's 32 centroid rows x 256 B
+    size_t rowbuf = c.take<char>(ROWBUF ? WAVES * rowbuf_wave : 0, ROWBUF ? 16 : 1);   // [WAVES] row buffers
+    size_t bq = c.take<s2h8>(B_LDS ? 2 * 8 * 64 : 0, 1);                 // the query operand [hi | lo][8][64] in MFMA lane order
+    size_t bytes = c.bytes;
+};
+static_assert(s2_mfma_lds<4, false, false>{}.bytes == 528 && s2_mfma_lds<4, true, false>{}.bytes == 33296 && s2_mfma_lds<16, true, true>{}.bytes == 149568,
+              "stage-2 recompute kernels' dynamic LDS");
+static_assert(2 * s2_mfma_lds<4, true, false>{}.bytes <= FLMR_LDS_CU_BYTES && s2_mfma_lds<16, true, true>{}.bytes <= FLMR_LDS_CU_BYTES,
+              "filter_stage2_lds_kernel: <4, false> two workgroups per CU, <16, true> one (no static LDS)");
+
 __global__ __launch_bounds__(256, 2) void filter_stage2_mfma_kernel(flmr_filter_args f, const int32_t* pids, int64_t pid_stride,
                                                                     const int32_t* counts, uint64_t* keys, int64_t key_stride,
                                                                     const _Float16* __restrict__ cen16,
@@ -522,9 +560,10 @@ __global__ __launch_bounds__(256, 2) void filter_stage2_mfma_kernel(flmr_filter_
     const int cnt = counts[b];
     const int qlen = f.q_lens ? f.q_lens[b] : f.nq_cand;
     const int nqc = qlen < f.nq_cand ? qlen : f.nq_cand;  // <= 32 on this path
-    float* tr = reinterpret_cast<float*>(smem) + (size_t)wave * 33;
+    constexpr s2_mfma_lds<4, false, false> L;
+    float* tr = reinterpret_cast<float*>(smem + L.tr) + wave * L.tr_wave;
     const int W = gridDim.y * 4, w = blockIdx.y * 4 + wave;
-    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // <= 64 documents per wave (launcher)
+    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // <= 64 documents per wave (flmr_doc_grid)
     if (ndw == 0) return;
     int my_pid = 0, my_len = 0;
     int64_t my_off = 0;
@@ -738,13 +777,13 @@ __global__ __launch_bounds__(64 * WAVES, B_LDS ? 1 : 2) void filter_stage2_lds_k
     const int cnt = counts[b];
     const int qlen = f.q_lens ? f.q_lens[b] : f.nq_cand;
     const int nqc = qlen < f.nq_cand ? qlen : f.nq_cand;  // <= 32 on this path
-    float* tr = reinterpret_cast<float*>(smem) + (size_t)wave * 33;
+    constexpr s2_mfma_lds<WAVES, true, B_LDS> L;
+    float* tr = reinterpret_cast<float*>(smem + L.tr) + wave * L.tr_wave;
     // this wave's row buffer: 32 centroid rows x 256 B, filled by direct global->LDS loads (16-byte pieces XOR-swizzled by row)
-    constexpr size_t TR_BYTES = (WAVES * 33 * sizeof(float) + 15) / 16 * 16;
-    char* rowbuf = smem + TR_BYTES + (size_t)wave * (32 * 256);
-    const s2h8* const Bh = reinterpret_cast<const s2h8*>(smem + TR_BYTES + (size_t)WAVES * (32 * 256));  // [8][64], then Bl [8][64]
+    char* rowbuf = smem + L.rowbuf + wave * L.rowbuf_wave;
+    const s2h8* const Bh = reinterpret_cast<const s2h8*>(smem + L.bq);  // [8][64], then Bl [8][64]
     if constexpr (B_LDS) {
-        s2h8* Bw = reinterpret_cast<s2h8*>(smem + TR_BYTES + (size_t)WAVES * (32 * 256));
+        s2h8* Bw = reinterpret_cast<s2h8*>(smem + L.bq);
         for (int t = threadIdx.x; t < 1024; t += 64 * WAVES) {
             const int lo = t >> 9, sidx = (t >> 6) & 7, ln = t & 63;
             const _Float16* src = (lo ? q_lo : q_hi) + ((size_t)b * f.ncol + (ln & 31)) * FLMR_DIM + 64 * (ln >> 5) + 8 * sidx;
@@ -753,7 +792,7 @@ __global__ __launch_bounds__(64 * WAVES, B_LDS ? 1 : 2) void filter_stage2_lds_k
         __syncthreads();
     }
     const int W = gridDim.y * WAVES, w = blockIdx.y * WAVES + wave;
-    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // <= 64 documents per wave (launcher)
+    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // <= 64 documents per wave (flmr_doc_grid)
     if (ndw == 0) return;
     int my_pid = 0, my_len = 0;
     int64_t my_off = 0;
@@ -876,33 +915,27 @@ int flmr_launch_filter_stage2_mfma(const flmr_filter_args& f, const int32_t* pid
 #ifndef FLMR_EXPERIMENTAL_VARIANTS
     if (form == s2_sw::regs || form == s2_sw::ldsb) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the regs / ldsb stage-2 gathers need a FLMR_EXPERIMENTAL_VARIANTS build");
 #endif
-    int G = (int)flmr_ceil_div(8192, 4 * (int64_t)f.nqueries);
-    const int gmin = (int)flmr_ceil_div(max_count, 4 * 64);
-    if (G < gmin) G = gmin;
-    if (G > (int)flmr_ceil_div(max_count, 4)) G = (int)flmr_ceil_div(max_count, 4);
-    if (G < 1) G = 1;
+    const int G = flmr_doc_grid(8192, 4, f.nqueries, max_count);
+    const size_t lds = s2_mfma_lds<4, true, false>{}.bytes;
 #ifdef FLMR_EXPERIMENTAL_VARIANTS
     // Measured losers, compiled only into a -DFLMR_EXPERIMENTAL_VARIANTS library (profiles/build_variant.py):
     // FLMR_S2_IMPL=regs: the first form of the kernel (per-lane half-row gathers into registers);
     // FLMR_S2_IMPL=ldsb: 16-wave blocks with the query operand in LDS (5.6 ms against 4.1 ms)
-    if (form == s2_sw::regs)
-        hipLaunchKernelGGL(filter_stage2_mfma_kernel, dim3(f.nqueries, G), dim3(256), 4 * 33 * sizeof(float), st, f, pids, pid_stride,
+    if (form == s2_sw::regs) {
+        const size_t ldsr = s2_mfma_lds<4, false, false>{}.bytes;
+        hipLaunchKernelGGL(filter_stage2_mfma_kernel, dim3(f.nqueries, G), dim3(256), ldsr, st, f, pids, pid_stride,
                            counts, keys, key_stride, cen16, q_hi, q_lo);
-    else if (form == s2_sw::ldsb) {
+    } else if (form == s2_sw::ldsb) {
         // 16-wave blocks sharing the query operand through LDS
-        int G16 = (int)flmr_ceil_div(8192, 16 * (int64_t)f.nqueries);
-        const int g16min = (int)flmr_ceil_div(max_count, 16 * 64);
-        if (G16 < g16min) G16 = g16min;
-        if (G16 > (int)flmr_ceil_div(max_count, 16)) G16 = (int)flmr_ceil_div(max_count, 16);
-        if (G16 < 1) G16 = 1;
-        const size_t lds16 = (16 * 33 * sizeof(float) + 15) / 16 * 16 + (size_t)16 * 32 * 256 + 16384;
+        const int G16 = flmr_doc_grid(8192, 16, f.nqueries, max_count);
+        const size_t lds16 = s2_mfma_lds<16, true, true>{}.bytes;
         FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(filter_stage2_lds_kernel<16, true>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
         hipLaunchKernelGGL((filter_stage2_lds_kernel<16, true>), dim3(f.nqueries, G16), dim3(1024), lds16, st, f, pids, pid_stride,
                            counts, keys, key_stride, cen16, q_hi, q_lo);
     } else
 #endif
-        hipLaunchKernelGGL((filter_stage2_lds_kernel<4, false>), dim3(f.nqueries, G), dim3(256), (4 * 33 * sizeof(float) + 15) / 16 * 16 + 4 * 32 * 256, st,
+        hipLaunchKernelGGL((filter_stage2_lds_kernel<4, false>), dim3(f.nqueries, G), dim3(256), lds, st,
                            f, pids, pid_stride, counts, keys, key_stride, cen16, q_hi, q_lo);
     FLMR_LAUNCH_CHECK();
     return FLMR_OK;
@@ -915,7 +948,7 @@ int flmr_launch_filter_stage2(const flmr_filter_args& f, const int32_t* pids, in
                               const int32_t* counts, int32_t max_count, uint64_t* keys, int64_t key_stride,
                               hipStream_t st) {
     if (max_count <= 0) return FLMR_OK;
-    const size_t lds = (size_t)S2_WAVES * (((f.nq_cand + 31) >> 5) * 32 + 1) * sizeof(float);
+    const size_t lds = s2_gather_lds{(f.nq_cand + 31) >> 5}.bytes;
     dim3 grid(f.nqueries, (unsigned)flmr_ceil_div(max_count, S2_WAVES)), block(S2_WAVES * 64);
     hipLaunchKernelGGL(filter_stage2_kernel, grid, block, lds, st, f, pids, pid_stride, counts, keys, key_stride);
     FLMR_LAUNCH_CHECK();

@@ -47,6 +47,17 @@ __device__ __forceinline__ void decompress_half_row(const uint8_t* __restrict__ 
     }
 }
 
+// dynamic LDS of the two one-document-per-workgroup kernels (maxsim_kernel, maxsim_gpu_fp16_kernel)
+template <int NBITS>
+struct s3_plain_lds {
+    int nq;
+    flmr_lds c;
+    size_t wlut = c.take<float>(256 * (8 / NBITS));   // [256 * VPB] (the fp16-numerics kernel: rounded to fp16, bucket_weights.half())
+    size_t colmax = c.take<int>(nq);                  // [nq] column maxima (order-preserving images)
+    size_t bytes = c.bytes;
+};
+static_assert(s3_plain_lds<2>{32}.bytes == 4224 && s3_plain_lds<8>{32}.bytes == 1152, "plain MaxSim kernels' dynamic LDS");
+
 template <int NBITS>
 __global__ __launch_bounds__(256) void maxsim_kernel(flmr_maxsim_args m, const int32_t* __restrict__ codes,
                                                      const uint8_t* __restrict__ residuals,
@@ -56,8 +67,9 @@ __global__ __launch_bounds__(256) void maxsim_kernel(flmr_maxsim_args m, const i
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int VPB = 8 / NBITS;
     constexpr int PACKED = FLMR_DIM / VPB;
-    float* wlut = reinterpret_cast<float*>(smem);                       // [256 * VPB]
-    int* colmax = reinterpret_cast<int*>(smem + 256 * VPB * sizeof(float));  // [nq]
+    const s3_plain_lds<NBITS> L{m.nq};
+    float* wlut = reinterpret_cast<float*>(smem + L.wlut);
+    int* colmax = reinterpret_cast<int*>(smem + L.colmax);
     const int b = blockIdx.x, d = y_base + blockIdx.y;
     if (d >= m.counts[b]) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -155,8 +167,9 @@ __global__ __launch_bounds__(256) void maxsim_gpu_fp16_kernel(flmr_maxsim_args m
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int VPB = 8 / NBITS;
     constexpr int PACKED = FLMR_DIM / VPB;
-    float* wlut = reinterpret_cast<float*>(smem);                            // [256 * VPB], rounded to fp16 (bucket_weights.half())
-    int* colmax = reinterpret_cast<int*>(smem + 256 * VPB * sizeof(float));  // [nq] order-preserving images
+    const s3_plain_lds<NBITS> L{m.nq};
+    float* wlut = reinterpret_cast<float*>(smem + L.wlut);
+    int* colmax = reinterpret_cast<int*>(smem + L.colmax);
     const int b = blockIdx.x, d = y_base + blockIdx.y;
     if (d >= m.counts[b]) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -454,6 +467,17 @@ __device__ __forceinline__ void s3_issue_rows(s3_raw<NBITS>& raw, const int* cdr
 // GPUF16 = true: the reference's CUDA-branch arithmetic (maxsim_gpu_fp16_kernel's, see there) on this kernel's wave-per-
 // document pipeline: fp16 embeddings by s3_decode_f16, ONE product per k-step against the fp16-rounded query, scores rounded
 // to fp16, rows past the passage's end excluded (-10000, no zero clamp), fp32 column sum rounded to fp16.  Nq <= 32.
+template <int NBITS>
+struct s3_regs_lds {
+    int nqp;
+    flmr_lds c;
+    size_t wlut = c.take<float>(256 * (8 / NBITS));   // [256 * VPB]
+    size_t colmax = c.take<float>(4 * nqp);           // [4 waves][nqp] each wave's running maxima
+    size_t colmax_wave = nqp;                         // (floats)
+    size_t bytes = c.bytes;
+};
+static_assert(s3_regs_lds<2>{32}.bytes == 4608 && s3_regs_lds<8>{32}.bytes == 1536, "maxsim_f16_kernel's dynamic LDS");
+
 template <int NBITS, bool GPUF16 = false>
 __global__ __launch_bounds__(256, 2) void maxsim_f16_kernel(flmr_maxsim_args m, const int32_t* __restrict__ codes,
                                                             const uint8_t* __restrict__ residuals,
@@ -462,10 +486,11 @@ __global__ __launch_bounds__(256, 2) void maxsim_f16_kernel(flmr_maxsim_args m, 
                                                             const float* __restrict__ wlut_g, int nqp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int VPB = 8 / NBITS;
-    float* wlut = reinterpret_cast<float*>(smem);  // [256 * VPB]
+    const s3_regs_lds<NBITS> L{nqp};
+    float* wlut = reinterpret_cast<float*>(smem + L.wlut);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
-    float* colmax = wlut + 256 * VPB + (size_t)wave * nqp;  // this wave's running maxima [nqp]
+    float* colmax = reinterpret_cast<float*>(smem + L.colmax) + wave * L.colmax_wave;  // this wave's running maxima [nqp]
     const int b = blockIdx.x;
     const int cnt = m.counts[b];
     const int qlen = m.q_lens ? m.q_lens[b] : m.nq;
@@ -475,7 +500,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_f16_kernel(flmr_maxsim_args m, 
     __syncthreads();
 
     const int W = gridDim.y * 4, w = blockIdx.y * 4 + wave;
-    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // documents of this wave (<= 64, guaranteed by the launcher)
+    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // documents of this wave (<= 64: flmr_doc_grid)
     if (ndw == 0) return;
     int my_pid = 0, my_len = 0;
     int64_t my_off = 0;
@@ -710,6 +735,16 @@ __device__ __forceinline__ float s3cw_tile_max(const f32x16& acch, const f32x16&
 }
 
 template <int NBITS>
+struct s3_cwregs_lds {
+    flmr_lds c;
+    size_t tab = c.take<char>(NBITS == 8 ? 1024 : 2 * 512 * (8 / NBITS));   // the fp16 hi / lo fragment tables (wtab16)
+    size_t colmax = c.take<float>(4 * 64);                                  // [4 waves][column maxima [32] | the current tile's row scales [32]]
+    size_t colmax_wave = 64;                                                // (floats)
+    size_t bytes = c.bytes;
+};
+static_assert(s3_cwregs_lds<2>{}.bytes == 5120 && s3_cwregs_lds<8>{}.bytes == 2048, "maxsim_cw_kernel's dynamic LDS");
+
+template <int NBITS>
 __global__ __launch_bounds__(256, 2) void maxsim_cw_kernel(flmr_maxsim_args m, const int32_t* __restrict__ codes,
                                                            const uint8_t* __restrict__ residuals,
                                                            const int64_t* __restrict__ doc_offsets,
@@ -717,20 +752,21 @@ __global__ __launch_bounds__(256, 2) void maxsim_cw_kernel(flmr_maxsim_args m, c
                                                            const uint32_t* __restrict__ wtab_g, const float* __restrict__ inv_norm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int VPB = 8 / NBITS;
-    constexpr int TAB_BYTES = NBITS == 8 ? 1024 : 2 * 512 * VPB;
+    constexpr s3_cwregs_lds<NBITS> L;
+    constexpr int TAB_BYTES = L.colmax - L.tab;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
-    float* colmax = reinterpret_cast<float*>(smem + TAB_BYTES) + (size_t)wave * 64;   // this wave's column maxima [32]
+    float* colmax = reinterpret_cast<float*>(smem + L.colmax) + wave * L.colmax_wave;   // this wave's column maxima [32]
     float* invs = colmax + 32;                                                           // the current tile's row scales [32]
     const int b = blockIdx.x;
     const int cnt = m.counts[b];
     const int qlen = m.q_lens ? m.q_lens[b] : m.nq;
-    for (int t = tid; t < TAB_BYTES / 4; t += 256) reinterpret_cast<uint32_t*>(smem)[t] = wtab_g[t];
+    for (int t = tid; t < TAB_BYTES / 4; t += 256) reinterpret_cast<uint32_t*>(smem + L.tab)[t] = wtab_g[t];
     if (lane < 32) colmax[lane] = 0.0f;
     __syncthreads();
 
     const int W = gridDim.y * 4, w = blockIdx.y * 4 + wave;
-    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // documents of this wave (<= 64, guaranteed by the launcher)
+    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // documents of this wave (<= 64: flmr_doc_grid)
     if (ndw == 0) return;
     int my_pid = 0, my_len = 0;
     int64_t my_off = 0;
@@ -775,7 +811,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_cw_kernel(flmr_maxsim_args m, c
         for (int t = 0; t < ntiles; t++) {
             // ---- the weights' fragments by table look-up; the row scales to LDS (0 for rows past the document's end) ----
             hf8 wh[8], wl[8];
-            s3cw_decode<NBITS>(smem, [&](int wi) { return (wi & 1) ? raw.r[wi >> 1].y : raw.r[wi >> 1].x; }, wh, wl);
+            s3cw_decode<NBITS>(smem + L.tab, [&](int wi) { return (wi & 1) ? raw.r[wi >> 1].y : raw.r[wi >> 1].x; }, wh, wl);
             if (h == 0) invs[i] = raw.valid ? raw.inv : 0.0f;
             // ---- centroid part: c . q_hi, c . q_lo (the registers of c are free for the next tile afterwards) ----
             f32x16 acch, accl;
@@ -895,7 +931,27 @@ struct s3_res {
 // CW = true: the same pipeline with the "centroid + weight" arithmetic of maxsim_cw_kernel (table = wtab16, one more load per
 // tile for the token's 1 / norm, 40 MFMAs and no decode arithmetic) -- the default S3 kernel: with the VALU work gone the
 // kernel is bound by how many row tiles it keeps in flight, and this pipeline keeps two per wave where the register form
-// keeps one.
+// keeps one.  Its LDS admits two workgroups per CU from nbits 2 (at nbits 1 the 8 KB table leaves one).
+template <int NBITS, bool CW>
+struct s3_dma_lds {
+    int nqp;
+    flmr_lds c;
+    size_t tab = c.take<float>(CW ? (NBITS == 8 ? 256 : 256 * (8 / NBITS)) : 256 * (8 / NBITS));   // wlut, or (CW) the fp16 hi / lo fragment tables
+    size_t colmax = c.take<float>(4 * (size_t)(nqp + 32));    // [4 waves][running maxima [nqp] | row scales [32]]
+    size_t colmax_wave = nqp + 32;                            // (floats)
+    size_t rowbuf_tile = 32 * FLMR_DIM * sizeof(_Float16);    // a tile's 32 centroid rows
+    size_t rowbuf_wave = 2 * rowbuf_tile;                     // tiles g and g + 1
+    size_t rowbuf = c.take<char>(4 * rowbuf_wave, 16);        // [4 waves][2][32 rows][256 B]
+    size_t ring_wave = 8 * 64 * sizeof(int32_t);              // the codes of eight tiles, one dword per lane
+    size_t ring = c.take<char>(4 * ring_wave);                // [4 waves][8][64]
+    size_t bytes = c.bytes;
+};
+static_assert(s3_dma_lds<1, true>{32}.bytes == 82944 && s3_dma_lds<2, true>{32}.bytes == 78848 && s3_dma_lds<4, true>{32}.bytes == 76800 &&
+              s3_dma_lds<8, true>{32}.bytes == 75776 && s3_dma_lds<8, false>{32}.bytes == 75776 && s3_dma_lds<2, false>{32}.bytes == 78848,
+              "maxsim_f16_dma_kernel's dynamic LDS at one query tile");
+static_assert(2 * s3_dma_lds<2, true>{32}.bytes <= FLMR_LDS_CU_BYTES,
+              "maxsim_f16_dma_kernel: two workgroups per CU from NBITS = 2 (no static LDS)");
+
 template <int NBITS, bool CW>
 __global__ __launch_bounds__(256, 2) void maxsim_f16_dma_kernel(flmr_maxsim_args m, const int32_t* __restrict__ codes,
                                                                 const uint8_t* __restrict__ residuals,
@@ -906,16 +962,17 @@ __global__ __launch_bounds__(256, 2) void maxsim_f16_dma_kernel(flmr_maxsim_args
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int VPB = 8 / NBITS, PACKED = FLMR_DIM * NBITS / 8, NB = 8 * NBITS;
     constexpr int RL = (NBITS == 1 ? 1 : NBITS / 2) + (CW ? 1 : 0);  // residual (+ 1 / norm) load instructions per tile
+    const s3_dma_lds<NBITS, CW> L{nqp};
     constexpr int TABF = CW ? (NBITS == 8 ? 256 : 256 * VPB) : 256 * VPB;   // table size in 32-bit words
-    float* wlut = reinterpret_cast<float*>(smem);  // [TABF]: wlut, or (CW) the fp16 hi / lo fragment tables
+    float* wlut = reinterpret_cast<float*>(smem + L.tab);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
-    float* colmax = wlut + TABF + (size_t)wave * (nqp + 32);  // this wave's running maxima [nqp] (nqp == 32 here) + row scales [32]
+    float* colmax = reinterpret_cast<float*>(smem + L.colmax) + wave * L.colmax_wave;  // (nqp == 32 here)
     float* invs = colmax + nqp;
-    char* const rowbuf = smem + ((TABF + 4 * (size_t)(nqp + 32)) * sizeof(float) + 15) / 16 * 16 + (size_t)wave * 16384;
+    char* const rowbuf = smem + L.rowbuf + wave * L.rowbuf_wave;
     const uint32_t rowbuf_lds =
         __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)rowbuf);
-    char* const ring = smem + ((TABF + 4 * (size_t)(nqp + 32)) * sizeof(float) + 15) / 16 * 16 + 4 * 16384 + (size_t)wave * 2048;
+    char* const ring = smem + L.ring + wave * L.ring_wave;
     const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring);
     const int b = blockIdx.x;
     const int cnt = m.counts[b];
@@ -925,7 +982,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_f16_dma_kernel(flmr_maxsim_args
     __syncthreads();
 
     const int W = gridDim.y * 4, w = blockIdx.y * 4 + wave;
-    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // documents of this wave (<= 64, guaranteed by the launcher)
+    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // documents of this wave (<= 64: flmr_doc_grid)
     if (ndw == 0) return;
     int my_pid = 0, my_len = 0;
     int64_t my_off = 0;
@@ -982,7 +1039,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_f16_dma_kernel(flmr_maxsim_args
     auto dma_rows = [&](int g, const int (&c)[8]) {
 #pragma unroll
         for (int gq = 0; gq < 8; gq++) {
-            const uint32_t dst = rowbuf_lds + (g & 1) * 8192 + gq * 1024;
+            const uint32_t dst = rowbuf_lds + (g & 1) * (uint32_t)L.rowbuf_tile + gq * 1024;
             uint32_t voff;
             asm volatile("s_mov_b32 m0, %2\n\tv_lshl_add_u32 %0, %3, 8, %4\n\tglobal_load_lds_dwordx4 %0, %1"
                          : "=&v"(voff)
@@ -1047,7 +1104,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_f16_dma_kernel(flmr_maxsim_args
         hf8 c[8];
 #pragma unroll
         for (int s = 0; s < 8; s++)
-            c[s] = *reinterpret_cast<const hf8*>(rowbuf + buf * 8192 + i * 256 + (((8 * h + s) ^ (i & 15)) << 4));
+            c[s] = *reinterpret_cast<const hf8*>(rowbuf + buf * L.rowbuf_tile + i * 256 + (((8 * h + s) ^ (i & 15)) << 4));
         int cc[8];
         ring_codes(g + 2, cc);
         // ---- the A operands: decompress + normalise + split, or (CW) the weights' fragments by table look-up ----
@@ -1145,6 +1202,18 @@ __global__ __launch_bounds__(256, 2) void maxsim_f16_dma_kernel(flmr_maxsim_args
 #define S3_BROW 136
 
 template <int NBITS>
+struct s3_multiq_lds {
+    flmr_lds c;
+    size_t wlut = c.take<float>(256 * (8 / NBITS));              // [256 * VPB]
+    size_t bq = c.take<_Float16>(S3_QC * 2 * 32 * S3_BROW);      // [S3_QC][hi|lo][32][S3_BROW] the staged query chunk
+    size_t colmax = c.take<float>(S3_MQW * (32 * S3_QC + 64));   // [S3_MQW waves][the chunk's column maxima | [64] running sums of the wave's docs]
+    size_t colmax_wave = 32 * S3_QC + 64;                        // (floats)
+    size_t bytes = c.bytes;
+};
+static_assert(s3_multiq_lds<2>{}.bytes == 153600 && s3_multiq_lds<8>{}.bytes == 150528, "maxsim_f16_multiq_kernel's dynamic LDS");
+static_assert(s3_multiq_lds<1>{}.bytes <= FLMR_LDS_CU_BYTES, "maxsim_f16_multiq_kernel: one workgroup per CU (no static LDS)");
+
+template <int NBITS>
 __global__ __launch_bounds__(64 * S3_MQW) void maxsim_f16_multiq_kernel(flmr_maxsim_args m, const int32_t* __restrict__ codes,
                                                                    const uint8_t* __restrict__ residuals,
                                                                    const int64_t* __restrict__ doc_offsets,
@@ -1152,18 +1221,19 @@ __global__ __launch_bounds__(64 * S3_MQW) void maxsim_f16_multiq_kernel(flmr_max
                                                                    const float* __restrict__ wlut_g, int nqp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int VPB = 8 / NBITS;
-    float* wlut = reinterpret_cast<float*>(smem);                                  // [256 * VPB]
-    _Float16* bq = reinterpret_cast<_Float16*>(smem + 256 * VPB * sizeof(float));  // [S3_QC][hi|lo][32][S3_BROW]
+    constexpr s3_multiq_lds<NBITS> L;
+    float* wlut = reinterpret_cast<float*>(smem + L.wlut);
+    _Float16* bq = reinterpret_cast<_Float16*>(smem + L.bq);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
-    float* colmax = reinterpret_cast<float*>(bq + S3_QC * 2 * 32 * S3_BROW) + (size_t)wave * (32 * S3_QC + 64);
+    float* colmax = reinterpret_cast<float*>(smem + L.colmax) + wave * L.colmax_wave;
     float* docsum = colmax + 32 * S3_QC;                                          // [64] running sums of this wave's docs
     const int b = blockIdx.x;
     const int cnt = m.counts[b];
     const int qlen = m.q_lens ? m.q_lens[b] : m.nq;
     for (int t = tid; t < 256 * VPB; t += 64 * S3_MQW) wlut[t] = wlut_g[t];
     const int W = gridDim.y * S3_MQW, w = blockIdx.y * S3_MQW + wave;
-    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // <= 64 (launcher); idle waves still join the barriers
+    const int ndw = cnt > w ? (cnt - w + W - 1) / W : 0;  // <= 64 (flmr_doc_grid); idle waves still join the barriers
     int my_pid = 0, my_len = 0;
     int64_t my_off = 0;
     if (lane < ndw) {
@@ -1298,7 +1368,8 @@ __global__ __launch_bounds__(64 * S3_MQW) void maxsim_f16_multiq_kernel(flmr_max
 // VMEM order per step g: codes(g+3) [2], residual bytes + 1/norm of tile g+2 [RL], rows of tile g+2 [8].  Top of step g needs
 // rows(g), residuals(g), codes(g+2): everything but the youngest 8 + RL operations (rows / residuals of tile g+1).  Requests
 // past the wave's last tile repeat the last tile (static counts, no branch); their data is never used.
-// grid = (nqueries, G), block = 256; LDS = table + 4 x (32 + 32 * 17 + 16) words + 4 x 16 KB.
+// grid = (nqueries, G), block = 256; LDS = table + 4 x (32 + 32 * 17 + 16) words + 4 x 16 KB: two workgroups per CU from nbits 2
+// (at nbits 1 the 8 KB of tables leave one).
 // ------------------------------------------------------------------------------------------------
 #define S3L_FLUSH 16                           // passages whose column maxima wait in LDS for their sums
 #define S3L_CBS 17                             // row stride (floats) of that [column][passage] matrix
@@ -1462,6 +1533,19 @@ struct s3l_codes {    // the eight codes of the rows this lane's DMA instruction
     __device__ __forceinline__ uint32_t at(int gq) const { return gq < 4 ? lo[gq] : hi[gq - 4]; }
 };
 
+struct s3l_lds {   // (the fragment tables are static LDS, see the kernel)
+    flmr_lds c;
+    size_t state_wave = S3L_WAVE_WORDS * sizeof(float);
+    size_t state = c.take<char>(4 * state_wave);              // [4 waves][row scales [32] | colbuf [32][S3L_CBS] | slots [S3L_FLUSH]]
+    size_t rowbuf_tile = 32 * FLMR_DIM * sizeof(_Float16);    // a tile's 32 centroid rows
+    size_t rowbuf_wave = 2 * rowbuf_tile;                     // the tiles of an even and an odd step
+    size_t rowbuf = c.take<char>(4 * rowbuf_wave, 16);        // [4 waves][2][32 rows][256 B]
+    size_t bytes = c.bytes;
+};
+static_assert(s3l_lds{}.bytes == 75008, "maxsim_lean_kernel's dynamic LDS");
+static_assert(2 * (s3l_lds{}.bytes + sizeof(uint32_t) * (256 * 4 + S3L_LO_PAD / 4) /* static: tab_s at NBITS = 2 */) <= FLMR_LDS_CU_BYTES,
+              "maxsim_lean_kernel: two workgroups per CU from NBITS = 2");
+
 template <int NBITS>
 __global__ __launch_bounds__(256, 2) void maxsim_lean_kernel(flmr_maxsim_args m, const int32_t* __restrict__ codes,
                                                              const uint8_t* __restrict__ residuals,
@@ -1480,10 +1564,11 @@ __global__ __launch_bounds__(256, 2) void maxsim_lean_kernel(flmr_maxsim_args m,
     // the fragment tables are a STATIC array: its LDS address is a constant that folds into the look-ups' offset fields (with the
     // dynamic carve-out's base the compiler adds a register holding "0" to each of a tile's 16 addresses)
     __shared__ __attribute__((aligned(16))) uint32_t tab_s[TABL];
-    float* const invs = reinterpret_cast<float*>(smem) + (size_t)wave * S3L_WAVE_WORDS;          // the tile's 32 row scales
+    constexpr s3l_lds L;
+    float* const invs = reinterpret_cast<float*>(smem + L.state + wave * L.state_wave);          // the tile's 32 row scales
     float* const colbuf = invs + 32;                                                             // [32 columns][S3L_CBS]
     int* const slots = reinterpret_cast<int*>(colbuf + 32 * S3L_CBS);                            // passage slot of each waiting sum
-    char* const rowbuf = smem + (4 * (size_t)S3L_WAVE_WORDS * 4 + 15) / 16 * 16 + (size_t)wave * 16384;
+    char* const rowbuf = smem + L.rowbuf + wave * L.rowbuf_wave;
     const uint32_t rowbuf_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)rowbuf);
     for (int t = tid; t < TABW; t += 256) tab_s[t < HIW ? t : t + (TABL - TABW)] = wtab_g[t];
     __syncthreads();
@@ -1521,7 +1606,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_lean_kernel(flmr_maxsim_args m,
 #endif
 #pragma unroll
         for (int gq = 0; gq < 8; gq++) {
-            const uint32_t dst = rowbuf_lds + par * 8192 + gq * 1024;
+            const uint32_t dst = rowbuf_lds + par * (uint32_t)L.rowbuf_tile + gq * 1024;
             const uint32_t po = piece_base ^ (uint32_t)(gq << 4);
             uint32_t voff;
             asm volatile("s_mov_b32 m0, %2\n\tv_lshl_add_u32 %0, %3, 8, %4\n\tglobal_load_lds_dwordx4 %0, %1"
@@ -1586,7 +1671,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_lean_kernel(flmr_maxsim_args m,
         r.touch(); cn.touch();
         hf8 c[8];
 #pragma unroll
-        for (int s = 0; s < 8; s++) c[s] = *reinterpret_cast<const hf8*>(rowbuf + par * 8192 + (rd_base ^ (uint32_t)(s << 4)));
+        for (int s = 0; s < 8; s++) c[s] = *reinterpret_cast<const hf8*>(rowbuf + par * L.rowbuf_tile + (rd_base ^ (uint32_t)(s << 4)));
         hf8 ah[8], al[8];
 #ifdef S3L_NO_DECODE
 #pragma unroll
@@ -1658,7 +1743,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_lean_kernel(flmr_maxsim_args m,
 template <int NBITS>
 static int launch_maxsim_lean_t(const flmr_maxsim_args& a, hipStream_t st, int G) {
     const flmr_index* ix = a.ix;
-    const size_t lds = (4 * (size_t)S3L_WAVE_WORDS * 4 + 15) / 16 * 16 + 4 * 16384;   // (+ the static fragment tables)
+    const size_t lds = s3l_lds{}.bytes;
     hipLaunchKernelGGL(s3_plan_kernel, dim3(a.nqueries), dim3(256), 0, st, a, ix->doc_offsets, ix->N, 4 * G);
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(maxsim_lean_kernel<NBITS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(maxsim_lean_kernel<NBITS>, dim3(a.nqueries, G), dim3(256), lds, st, a, ix->codes, ix->residuals, ix->centroids_f16,
@@ -1819,6 +1904,17 @@ __device__ unsigned long long s3q_prof[64];
 // the matrix pipe while the other decodes, gathers or waits, without any hand-made stagger; the price is a decode per 8 instead
 // of 16 q-tiles, and it is the slower form (Nq = 832: 5.59 vs 5.03 ms per 256 queries: what a SIMD issues beside its MFMAs adds to
 // their time instead of hiding behind it, and this form issues more per MFMA).
+template <int R>
+struct s3q_lds {   // (wlut is static LDS)
+    flmr_lds c;
+    size_t ring = c.take<char>(2 * R * S3Q_SLOT);   // [2][R] decoded tiles: [k-step][hi | lo][lane] 16-byte fragments
+    size_t raw = c.take<char>(2 * R * S3Q_RAW);     // [2][R] gathered centroid rows
+    size_t bytes = c.bytes;
+};
+static_assert(s3q_lds<3>{}.bytes == 147456 && s3q_lds<1>{}.bytes == 49152, "maxsim_qs_kernel's dynamic LDS");
+static_assert(s3q_lds<3>{}.bytes + 256 * 8 * sizeof(float) <= FLMR_LDS_CU_BYTES && 2 * (s3q_lds<1>{}.bytes + 256 * 8 * sizeof(float)) <= FLMR_LDS_CU_BYTES,
+              "maxsim_qs_kernel: <8, 3> one workgroup per CU, <4, 1> two (static: wlut_s, 256 * VPB floats, most at NBITS = 1)");
+
 template <int NBITS, int NW, int R>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void maxsim_qs_kernel(flmr_maxsim_args m, const int32_t* __restrict__ codes,
                                                         const uint8_t* __restrict__ residuals,
@@ -1833,8 +1929,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void maxsim_qs_kernel(flm
     constexpr int KD = 8 / ND;             // k-steps of a tile a decoding wave handles: wave, wave + 4
     constexpr int UD = R * KD;             // decode units per round and decoding wave
     __shared__ __attribute__((aligned(16))) float wlut_s[256 * VPB];
-    char* const ring = smem;                                  // [2][R] decoded tiles: [k-step][hi | lo][lane] 16-byte fragments
-    char* const raw = smem + 2 * R * S3Q_SLOT;                // [2][R] gathered centroid rows
+    constexpr s3q_lds<R> L;
+    char* const ring = smem + L.ring;
+    char* const raw = smem + L.raw;
     const uint32_t raw_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)raw);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2114,7 +2211,7 @@ static int launch_maxsim_qs_nw(const flmr_maxsim_args& a, hipStream_t st, int nq
     if (Y > tiles_bound / 24) Y = (int)(tiles_bound / 24);
     if (Y > a.plan_wcap - 1) Y = a.plan_wcap - 1;
     if (Y < 1) Y = 1;
-    const size_t lds = (size_t)2 * R * (S3Q_SLOT + S3Q_RAW);
+    const size_t lds = s3q_lds<R>{}.bytes;
     float* qscale = a.colmax_ws + (size_t)a.nqueries * a.key_stride * (size_t)nqp;   // [nqueries], behind the column maxima
     hipLaunchKernelGGL(s3q_scale_kernel, dim3(a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq, qscale);
     hipLaunchKernelGGL(s3q_split_q, dim3((nqp * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq, nqp, a.q_hi, a.q_lo, qscale);
@@ -2135,13 +2232,9 @@ static int launch_maxsim_qs_t(const flmr_maxsim_args& a, hipStream_t st, int nqp
 #endif
 }
 
-// waves per query of the one-tile kernels: enough to fill the chip, at most 64 documents per wave, at least 1
+// workgroups per query of the one-tile kernels (flmr_doc_grid)
 static int s3_waves(const flmr_maxsim_args& a) {
-    int G = (int)flmr_ceil_div(4096, 4 * (int64_t)a.nqueries);
-    const int gmin = (int)flmr_ceil_div(a.max_count, 4 * 64);
-    if (G < gmin) G = gmin;
-    if (G > (int)flmr_ceil_div(a.max_count, 4)) G = (int)flmr_ceil_div(a.max_count, 4);
-    if (G < 1) G = 1;
+    int G = flmr_doc_grid(4096, 4, a.nqueries, a.max_count);
 #ifdef S3L_G
     G = S3L_G;
 #endif
@@ -2189,7 +2282,7 @@ template <int NBITS>
 static int launch_maxsim_f16_t(const flmr_maxsim_args& a, s3_form form, hipStream_t st) {
     const flmr_index* ix = a.ix;
     const int nqp = (int)flmr_round_up(a.nq, 32);
-    const size_t lds = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)4 * nqp * sizeof(float);
+    const size_t lds = s3_regs_lds<NBITS>{nqp}.bytes;
     if (lds > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large for the MaxSim kernel's LDS column maxima", a.nq);
     if (!(ix->centroids_f16_exact && ix->centroids_f16 && a.q_hi && a.q_lo))
         FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the fp16 MaxSim kernels need fp16-exact centroids and split buffers");
@@ -2209,13 +2302,8 @@ static int launch_maxsim_f16_t(const flmr_maxsim_args& a, s3_form form, hipStrea
                            a.q_hi, a.q_lo);
     const int G = s3_waves(a);
     if (form == s3_form::multiq) {
-        const size_t lds2 = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)S3_QC * 2 * 32 * S3_BROW * sizeof(_Float16) +
-                            (size_t)S3_MQW * (32 * S3_QC + 64) * sizeof(float);
-        int G2 = (int)flmr_ceil_div(4096, S3_MQW * (int64_t)a.nqueries);
-        const int g2min = (int)flmr_ceil_div(a.max_count, S3_MQW * 64);
-        if (G2 < g2min) G2 = g2min;
-        if (G2 > (int)flmr_ceil_div(a.max_count, S3_MQW)) G2 = (int)flmr_ceil_div(a.max_count, S3_MQW);
-        if (G2 < 1) G2 = 1;
+        const size_t lds2 = s3_multiq_lds<NBITS>{}.bytes;
+        const int G2 = flmr_doc_grid(4096, S3_MQW, a.nqueries, a.max_count);
         FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(maxsim_f16_multiq_kernel<NBITS>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
         hipLaunchKernelGGL(maxsim_f16_multiq_kernel<NBITS>, dim3(a.nqueries, G2), dim3(64 * S3_MQW), lds2, st, a, ix->codes,
@@ -2226,11 +2314,10 @@ static int launch_maxsim_f16_t(const flmr_maxsim_args& a, s3_form form, hipStrea
         if (rc) return rc;
     } else if (form == s3_form::cw) {
         // centroid + weight form on the LDS-DMA pipeline (the default for one query tile; 32-bit row offsets: table < 4 GB)
-        const size_t tabw = NBITS == 8 ? 256 : 256 * (8 / NBITS);
 #ifdef S3_LDS_PAD   // development probe: a larger request leaves one workgroup per CU (one wave per SIMD)
-        const size_t lds4 = ((tabw + (size_t)4 * (nqp + 32)) * sizeof(float) + 15) / 16 * 16 + 4 * 16384 + 4 * 2048 + S3_LDS_PAD;
+        const size_t lds4 = s3_dma_lds<NBITS, true>{nqp}.bytes + S3_LDS_PAD;
 #else
-        const size_t lds4 = ((tabw + (size_t)4 * (nqp + 32)) * sizeof(float) + 15) / 16 * 16 + 4 * 16384 + 4 * 2048;
+        const size_t lds4 = s3_dma_lds<NBITS, true>{nqp}.bytes;
 #endif
         FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(maxsim_f16_dma_kernel<NBITS, true>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
@@ -2238,12 +2325,12 @@ static int launch_maxsim_f16_t(const flmr_maxsim_args& a, s3_form form, hipStrea
                            ix->doc_offsets, ix->centroids_f16, reinterpret_cast<const float*>(ix->wtab16), nqp, ix->inv_norm);
     } else if (form == s3_form::cwregs) {
         // the same arithmetic with register row gathers, one tile in flight (A/B runs; bit-identical to the default)
-        const size_t lds4 = (size_t)(NBITS == 8 ? 1024 : 2 * 512 * (8 / NBITS)) + (size_t)4 * 64 * sizeof(float);
+        const size_t lds4 = s3_cwregs_lds<NBITS>{}.bytes;
         hipLaunchKernelGGL(maxsim_cw_kernel<NBITS>, dim3(a.nqueries, G), dim3(256), lds4, st, a, ix->codes, ix->residuals,
                            ix->doc_offsets, ix->centroids_f16, ix->wtab16, ix->inv_norm);
     } else if (form == s3_form::dma) {
         // (measured, 1 M passages: nbits = 2  2.03 vs 2.04 ms for the register form; nbits = 8  2.31 vs 2.43 ms)
-        const size_t lds3 = (((size_t)256 * (8 / NBITS) + (size_t)4 * (nqp + 32)) * sizeof(float) + 15) / 16 * 16 + 4 * 16384 + 4 * 2048;
+        const size_t lds3 = s3_dma_lds<NBITS, false>{nqp}.bytes;
         FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(maxsim_f16_dma_kernel<NBITS, false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
         hipLaunchKernelGGL((maxsim_f16_dma_kernel<NBITS, false>), dim3(a.nqueries, G), dim3(256), lds3, st, a, ix->codes, ix->residuals,
@@ -2259,7 +2346,7 @@ static int launch_maxsim_f16_t(const flmr_maxsim_args& a, s3_form form, hipStrea
 template <int NBITS>
 static int launch_maxsim_t(const flmr_maxsim_args& a, hipStream_t st) {
     const flmr_index* ix = a.ix;
-    const size_t lds = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)a.nq * sizeof(int);
+    const size_t lds = s3_plain_lds<NBITS>{a.nq}.bytes;
     if (lds > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large for the MaxSim kernel's LDS column maxima", a.nq);
     for (int y0 = 0; y0 < a.max_count; y0 += 32768) {
         const int ny = (a.max_count - y0) < 32768 ? (a.max_count - y0) : 32768;
@@ -2274,14 +2361,10 @@ template <int NBITS>
 static int launch_maxsim_f16_gpunum_t(const flmr_maxsim_args& a, hipStream_t st) {
     const flmr_index* ix = a.ix;
     const int nqp = 32;
-    const size_t lds = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)4 * nqp * sizeof(float);
+    const size_t lds = s3_regs_lds<NBITS>{nqp}.bytes;
     hipLaunchKernelGGL(s3_split_q, dim3((nqp * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq, nqp,
                        a.q_hi, a.q_lo);   // q_hi = half(Q): the only image this mode reads
-    int G = (int)flmr_ceil_div(4096, 4 * (int64_t)a.nqueries);
-    const int gmin = (int)flmr_ceil_div(a.max_count, 4 * 64);
-    if (G < gmin) G = gmin;
-    if (G > (int)flmr_ceil_div(a.max_count, 4)) G = (int)flmr_ceil_div(a.max_count, 4);
-    if (G < 1) G = 1;
+    const int G = flmr_doc_grid(4096, 4, a.nqueries, a.max_count);
     hipLaunchKernelGGL((maxsim_f16_kernel<NBITS, true>), dim3(a.nqueries, G), dim3(256), lds, st, a, ix->codes, ix->residuals,
                        ix->doc_offsets, ix->centroids_f16, ix->wlut, nqp);
     FLMR_LAUNCH_CHECK();
@@ -2291,7 +2374,7 @@ static int launch_maxsim_f16_gpunum_t(const flmr_maxsim_args& a, hipStream_t st)
 template <int NBITS>
 static int launch_maxsim_gpu_fp16_t(const flmr_maxsim_args& a, hipStream_t st) {
     const flmr_index* ix = a.ix;
-    const size_t lds = (size_t)256 * (8 / NBITS) * sizeof(float) + (size_t)a.nq * sizeof(int);
+    const size_t lds = s3_plain_lds<NBITS>{a.nq}.bytes;
     if (lds > 64 * 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "nq=%d too large for the MaxSim kernel's LDS column maxima", a.nq);
     for (int y0 = 0; y0 < a.max_count; y0 += 32768) {
         const int ny = (a.max_count - y0) < 32768 ? (a.max_count - y0) : 32768;

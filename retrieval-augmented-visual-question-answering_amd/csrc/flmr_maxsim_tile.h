@@ -14,9 +14,20 @@
 #define MT_QC 4        // query tiles of 32 rows staged per pass
 #define MT_BROW 136    // LDS row pitch in halves
 
-// bytes of the staged query planes (PL = 2: hi | lo; 1: hi only)
-template <int PL>
-static constexpr size_t mt_stage_bytes() { return (size_t)MT_QC * PL * 32 * MT_BROW * sizeof(_Float16); }
+// The three kernels' dynamic LDS: the staged query planes (PL = 2: hi | lo; 1: hi only), the column state (COL = mt_col_t<ARGMAX>)
+// and, behind it, `table` bytes of the document loader's own (the gathered kernel's decode table; 16-byte aligned: nqp % 32 == 0)
+template <int PL, class COL>
+struct mt_lds {
+    int nqp;
+    size_t table = 0;
+    flmr_lds c;
+    size_t bq = c.take<_Float16>(MT_QC * PL * 32 * MT_BROW);   // [MT_QC][PL][32][MT_BROW]
+    size_t cols = c.take<COL>(nqp);                            // [nqp] column state
+    size_t ltab = c.take<char>(table);
+    size_t bytes = c.bytes;
+};
+static_assert(mt_lds<2, unsigned int>{32}.bytes == 69760 && mt_lds<2, unsigned long long>{32}.bytes == 69888 &&
+              mt_lds<1, unsigned int>{32}.bytes == 34944 && mt_lds<2, unsigned long long>{32, 4096}.bytes == 73984, "padded MaxSim kernels' dynamic LDS at one query tile");
 // query tiles of the chunk that starts at row qc0
 __device__ __forceinline__ int mt_chunk_tiles(int nq, int qc0) { return ((nq - qc0 < 32 * MT_QC ? nq - qc0 : 32 * MT_QC) + 31) >> 5; }
 

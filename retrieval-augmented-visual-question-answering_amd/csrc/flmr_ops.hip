@@ -297,8 +297,9 @@ __global__ __launch_bounds__(256, 2) void colbert_score_padded_mfma_kernel(const
                                                                            const uint8_t* __restrict__ mask, int Ld,
                                                                            float* out, float* colmax_out, int32_t* argmax_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* bq = reinterpret_cast<_Float16*>(smem);                                            // [MT_QC][hi|lo][32][MT_BROW]
-    mt_col_t<ARGMAX>* cols = reinterpret_cast<mt_col_t<ARGMAX>*>(bq + MT_QC * 2 * 32 * MT_BROW);   // [nqp] column state
+    const mt_lds<2, mt_col_t<ARGMAX>> L{nqp};
+    _Float16* bq = reinterpret_cast<_Float16*>(smem + L.bq);
+    mt_col_t<ARGMAX>* cols = reinterpret_cast<mt_col_t<ARGMAX>*>(smem + L.cols);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
     // gridDim.y > 1: the CROSS form -- every query (blockIdx.y) against every document, out [gridDim.y, B]
@@ -368,7 +369,7 @@ static int score_padded_form(score_form form, const float* Q, int32_t q_batch, i
         RUN(sc.alloc(&qh, (size_t)q_batch * nqp * FLMR_DIM));
         RUN(sc.alloc(&ql, (size_t)q_batch * nqp * FLMR_DIM));
         hipLaunchKernelGGL(score_split_q, dim3(1024), dim3(256), 0, st, Q, q_batch, nq, nqp, qh, ql);
-        const size_t lds = mt_stage_bytes<2>() + (size_t)nqp * sizeof(unsigned int);
+        const size_t lds = mt_lds<2, mt_col_t<false>>{nqp}.bytes;
         FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_padded_mfma_kernel<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(colbert_score_padded_mfma_kernel<false>, grid, dim3(256), lds, st, qh, ql, nullptr, q_batch, nq, nqp, D,
@@ -422,7 +423,7 @@ extern "C" int flmr_colbert_maxsim_fwd(const float* Q, int32_t q_batch, int32_t 
     const dim3 grid((unsigned)B, cross ? (unsigned)q_batch : 1u);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nqp = (int)flmr_round_up(nq, 32);
-    const size_t lds = mt_stage_bytes<2>() + (size_t)nqp * sizeof(unsigned long long);
+    const size_t lds = mt_lds<2, mt_col_t<true>>{nqp}.bytes;
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_padded_mfma_kernel<true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(colbert_score_padded_mfma_kernel<true>, grid, dim3(256), lds, st, nullptr, nullptr, Q, q_batch, nq, nqp,

@@ -43,7 +43,7 @@ struct rs_store_loader {
     const void* store;
     const uint8_t* store_mask;
     int npassages, Ld;
-    static size_t lds_bytes() { return 0; }
+    __host__ __device__ static constexpr size_t lds_bytes() { return 0; }
     __device__ __forceinline__ void stage(char*, int) const {}
     __device__ __forceinline__ rs_doc open(int pid) const {
         rs_doc d;
@@ -93,7 +93,7 @@ struct rs_index_loader {
     const float* wlut;
     int64_t num_passages, pid_base;
     int K;
-    static size_t lds_bytes() { return (size_t)256 * VPB * sizeof(float); }
+    __host__ __device__ static constexpr size_t lds_bytes() { return (size_t)256 * VPB * sizeof(float); }
     __device__ __forceinline__ void stage(char* lds, int tid) const {
         float* t = reinterpret_cast<float*>(lds);
         for (int e = tid; e < 256 * VPB; e += 256) t[e] = wlut[e];
@@ -208,13 +208,14 @@ __global__ __launch_bounds__(256, 2) void maxsim_gather_fwd_kernel(const float* 
                                                                    const int32_t* __restrict__ pids, int k,
                                                                    float* out, float* colmax_out, int32_t* argmax_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* bq = reinterpret_cast<_Float16*>(smem);                                                   // [MT_QC][hi|lo][32][MT_BROW]
-    unsigned long long* colkey = reinterpret_cast<unsigned long long*>(bq + MT_QC * 2 * 32 * MT_BROW);   // [nqp] (value, ~token)
+    const mt_lds<2, unsigned long long> Y{nqp, L::lds_bytes()};
+    _Float16* bq = reinterpret_cast<_Float16*>(smem + Y.bq);
+    unsigned long long* colkey = reinterpret_cast<unsigned long long*>(smem + Y.cols);   // [nqp] (value, ~token)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
     const size_t ob = blockIdx.x;
     const size_t qrow0 = (ob / (size_t)k) * nq;
-    const char* ltab = reinterpret_cast<const char*>(colkey + nqp);   // the loader's own LDS (16-byte aligned: nqp % 32 == 0)
+    const char* ltab = smem + Y.ltab;   // the loader's own LDS
     const rs_doc doc = ld.open(pids[ob]);
     const bool live = doc.live;
     const int Ld = doc.len;
@@ -296,7 +297,7 @@ template <class L>
 static int launch_fwd(const L& ld, const float* Q, int32_t nqueries, int32_t nq, const int32_t* pids, int32_t k, float* out, float* colmax,
                       int32_t* argmax, hipStream_t st) {
     const int nqp = (int)((nq + 31) / 32 * 32);
-    const size_t lds = mt_stage_bytes<2>() + (size_t)nqp * sizeof(unsigned long long) + L::lds_bytes();
+    const size_t lds = mt_lds<2, unsigned long long>{nqp, L::lds_bytes()}.bytes;
     const dim3 grid((unsigned)((int64_t)nqueries * k));
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(maxsim_gather_fwd_kernel<L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(maxsim_gather_fwd_kernel<L>, grid, dim3(256), lds, st, Q, (int)nq, nqp, ld, pids, (int)k, out, colmax, argmax);

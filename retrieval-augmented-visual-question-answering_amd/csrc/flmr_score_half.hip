@@ -24,8 +24,9 @@ __global__ __launch_bounds__(256, 2) void colbert_score_half_kernel(const void* 
                                                                     float* colmax_out, int32_t* argmax_out) {
     constexpr int PL = QF16 ? 1 : 2;   // staged planes per query tile: hi | hi, lo
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* bq = reinterpret_cast<_Float16*>(smem);                                             // [MT_QC][PL][32][MT_BROW]
-    mt_col_t<ARGMAX>* cols = reinterpret_cast<mt_col_t<ARGMAX>*>(bq + MT_QC * PL * 32 * MT_BROW);   // [nqp] column state
+    const mt_lds<PL, mt_col_t<ARGMAX>> L{nqp};
+    _Float16* bq = reinterpret_cast<_Float16*>(smem + L.bq);
+    mt_col_t<ARGMAX>* cols = reinterpret_cast<mt_col_t<ARGMAX>*>(smem + L.cols);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
     const size_t ob = (size_t)blockIdx.y * gridDim.x + b;
@@ -83,7 +84,7 @@ static int sh_launch(const void* Q, int32_t q_batch, int32_t nq, const void* D, 
                      float* out, float* colmax, int32_t* argmax, hipStream_t st) {
     const dim3 grid((unsigned)B, cross ? (unsigned)q_batch : 1u);
     const int nqp = (int)flmr_round_up(nq, 32);
-    const size_t lds = mt_stage_bytes<(QF16 ? 1 : 2)>() + (size_t)nqp * (ARGMAX ? sizeof(unsigned long long) : sizeof(unsigned int));
+    const size_t lds = mt_lds<(QF16 ? 1 : 2), mt_col_t<ARGMAX>>{nqp}.bytes;
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(colbert_score_half_kernel<ARGMAX, QF16>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((colbert_score_half_kernel<ARGMAX, QF16>), grid, dim3(256), lds, st, Q, (int)q_batch, (int)nq, nqp,

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void s0_split_q(const float* Q, const int32_t*
 #define S0_WAVES 8               // waves per block (512 threads): two per SIMD, so one wave's MFMAs overlap the other's epilogue
 #endif
 #ifndef S0_OCC
-#define S0_OCC 2                // workgroups per CU the register budget is sized for
+#define S0_OCC 2                // workgroups per CU the register budget is sized for (s0_centroid_scores_f16's 132 KB of LDS leave one resident)
 #endif
 #define S0_BROW 136             // halfs per staged B row (128 + 8 pad: conflict-free ds_read_b128 across rows)
 #ifndef S0_DMA_B
@@ -193,6 +193,19 @@ __global__ __launch_bounds__(256) void s0_split_q(const float* Q, const int32_t*
 // tile-level "anything survives?" test is scalar; only a tile that does hold a surviving row (rare) goes through the LDS
 // staging + row stores of the dense epilogue.  That halves the kernel's LDS traffic, which at 16 KB of B fragments +
 // 8 KB of staging per (wave, query) was as long as its MFMA time.
+#define S0_TILE_BYTES (32 * FLMR_DIM * (int)sizeof(_Float16))   // a tile's 32 fp16 rows, unpadded (the DMA-ed operands of all three kernels)
+
+struct s0_f16_lds {
+    flmr_lds c;
+    size_t stage_wave = 32 * S0_LDS_STRIDE;                  // (floats)
+    size_t stage = c.take<float>(S0_WAVES * stage_wave);     // [S0_WAVES][32 rows][S0_LDS_STRIDE] staging tiles of the table stores (!SPARSE only)
+    size_t bq = c.take<char>(S0_DMA_B ? 2 * S0_DCH * 2 * S0_TILE_BYTES                                   // [2][S0_DCH][hi | lo] DMA-ed tiles
+                                      : S0_CH * 2 * 32 * S0_BROW * sizeof(_Float16));                    // [S0_CH][hi | lo][32][S0_BROW]
+    size_t bytes = c.bytes;
+};
+static_assert(s0_f16_lds{}.bytes == (S0_DMA_B ? 135168 : 141312), "s0_centroid_scores_f16's dynamic LDS");
+static_assert(s0_f16_lds{}.bytes <= FLMR_LDS_CU_BYTES, "s0_centroid_scores_f16: no static LDS");
+
 template <bool ARGMAX, bool SPARSE>
 __global__ __launch_bounds__(64 * S0_WAVES, S0_OCC) void s0_centroid_scores_f16(flmr_s0_args a) {
     // dynamic LDS: [4 waves][32 rows][36 f32] staging tiles for the row-contiguous table stores, then the fp16 B
@@ -203,8 +216,9 @@ __global__ __launch_bounds__(64 * S0_WAVES, S0_OCC) void s0_centroid_scores_f16(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
-    float* stage = reinterpret_cast<float*>(smem) + wave * 32 * S0_LDS_STRIDE;  // (!SPARSE only)
-    _Float16* bq = reinterpret_cast<_Float16*>(smem + S0_WAVES * 32 * S0_LDS_STRIDE * sizeof(float));
+    constexpr s0_f16_lds L;
+    float* stage = reinterpret_cast<float*>(smem + L.stage) + wave * L.stage_wave;
+    _Float16* bq = reinterpret_cast<_Float16*>(smem + L.bq);
     const int wtile = blockIdx.x * S0_WAVES + wave;  // (32*S0_RT)-row tile index == partial block index
     const int row0 = wtile * 32 * S0_RT;
     const bool active = row0 < a.K;  // the launcher guarantees K % (32*S0_RT) == 0; idle waves still join the barriers
@@ -246,7 +260,7 @@ __global__ __launch_bounds__(64 * S0_WAVES, S0_OCC) void s0_centroid_scores_f16(
                 const int bb = blockIdx.y + (itx / T) * gridDim.y, row = 4 * g + (lane >> 4);
                 const _Float16* src = (hl ? a.q_lo : a.q_hi) + ((size_t)bb * a.ncol + (itx % T) * 32 + row) * FLMR_DIM +
                                       (((lane & 15) ^ (row & 15)) << 3);
-                __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(bqb + (((buf * S0_DCH + item) * 2 + hl) * 8192 + g * 1024)),
+                __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(bqb + (((buf * S0_DCH + item) * 2 + hl) * S0_TILE_BYTES + g * 1024)),
                                                  16, 0, 0);
             }
         }
@@ -264,8 +278,8 @@ __global__ __launch_bounds__(64 * S0_WAVES, S0_OCC) void s0_centroid_scores_f16(
         const int b = blockIdx.y + (it / T) * gridDim.y, ct = it % T;
         f16x8 bh[8], bl[8];
         {
-            const char* ph = bqb + (((buf * S0_DCH + j) * 2 + 0) * 8192) + i * 256;
-            const char* pl = bqb + (((buf * S0_DCH + j) * 2 + 1) * 8192) + i * 256;
+            const char* ph = bqb + (((buf * S0_DCH + j) * 2 + 0) * S0_TILE_BYTES) + i * 256;
+            const char* pl = bqb + (((buf * S0_DCH + j) * 2 + 1) * S0_TILE_BYTES) + i * 256;
 #pragma unroll
             for (int s = 0; s < 8; s++) {
                 bh[s] = *reinterpret_cast<const f16x8*>(ph + (((8 * h + s) ^ (i & 15)) << 4));
@@ -444,14 +458,25 @@ __device__ __forceinline__ void s0q_wait_vm() {
 // the block maxima as they are (s0_select_cells knows they are within q_err of the full values and verifies its choice), and
 // the lo products are computed only for a tile in which  ah + q_err >= thr  somewhere -- a tile that can hold a surviving row,
 // a few dozen of a query's 4096 -- after which the dense epilogue tests and stores the FULL values exactly as before.
+struct s0q_lds {
+    flmr_lds c;
+    size_t stage_wave = 32 * S0_LDS_STRIDE;                  // (floats)
+    size_t stage = c.take<float>(8 * stage_wave);            // [8 waves][32 rows][S0_LDS_STRIDE] staging tiles of the dense epilogue
+    size_t abuf = c.take<char>(S0Q_NBUF * 2 * S0_TILE_BYTES);   // [S0Q_NBUF][2] tiles of the centroid stream (64-row blocks)
+    size_t bytes = c.bytes;
+};
+static_assert(s0q_lds{}.bytes == 86016, "s0_centroid_scores_qs's dynamic LDS");
+static_assert(s0q_lds{}.bytes <= FLMR_LDS_CU_BYTES, "s0_centroid_scores_qs: one workgroup per CU (no static LDS)");
+
 template <bool HI_ONLY, bool APPROX = false>
 __global__ __launch_bounds__(512, 1) void s0_centroid_scores_qs(flmr_s0_args a, int rows_per_slice) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform for the compiler too: the queries' addresses stay in scalar registers
     const int i = lane & 31, h = lane >> 5;
-    float* stage = reinterpret_cast<float*>(smem) + wave * 32 * S0_LDS_STRIDE;
-    char* const abuf = smem + 8 * 32 * S0_LDS_STRIDE * sizeof(float);
+    constexpr s0q_lds L;
+    float* stage = reinterpret_cast<float*>(smem + L.stage) + wave * L.stage_wave;
+    char* const abuf = smem + L.abuf;
     const uint32_t abuf_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)abuf);
     const int row_begin = blockIdx.y * rows_per_slice;
     const int row_end = row_begin + rows_per_slice < a.K ? row_begin + rows_per_slice : a.K;  // multiples of 64
@@ -495,7 +520,7 @@ __global__ __launch_bounds__(512, 1) void s0_centroid_scores_qs(flmr_s0_args a, 
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const uint32_t voff = (uint32_t)(row_begin + 64 * pp + 32 * u + prow) * 256u + poff;  // K * 256 < 4 GB (launcher)
-            const uint32_t dst = __builtin_amdgcn_readfirstlane(abuf_lds + ((p % S0Q_NBUF) * 2 + u) * 8192 + wave * 1024);
+            const uint32_t dst = __builtin_amdgcn_readfirstlane(abuf_lds + ((p % S0Q_NBUF) * 2 + u) * S0_TILE_BYTES + wave * 1024);
             asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" ::"v"(voff), "s"(dst), "s"(a.centroids_f16) : "memory", "m0");
         }
     };
@@ -570,7 +595,7 @@ __global__ __launch_bounds__(512, 1) void s0_centroid_scores_qs(flmr_s0_args a, 
         for (int u = 0; u < 2; u++) {
             f16x8 av[8];
             {
-                const char* pa = abuf + __builtin_amdgcn_readfirstlane(((p % S0Q_NBUF) * 2 + u) * 8192);   // (scalar: one add per read)
+                const char* pa = abuf + __builtin_amdgcn_readfirstlane(((p % S0Q_NBUF) * 2 + u) * S0_TILE_BYTES);   // (scalar: one add per read)
 #pragma unroll
                 for (int s = 0; s < 8; s++) av[s] = *reinterpret_cast<const f16x8*>(pa + aoff[s]);
             }
@@ -689,15 +714,29 @@ __device__ unsigned long long s0q_prof[8];
 #define S0Q2_GRP 8     // 64-row blocks per group of the coarse column maxima (512 rows; a multiple of the blocks of a step)
 #define S0Q2_NBUF 4    // super-block buffers of S0Q2_SBT x 8 KB (the staging rows of the deferred pass reuse them)
 
+struct s0q2_lds {
+    flmr_lds c;
+    size_t abuf = c.take<char>(S0Q2_NBUF * S0Q2_SBT * S0_TILE_BYTES);   // [S0Q2_NBUF][S0Q2_SBT] tiles of the centroid stream
+    size_t stage = abuf;                                     // ALIAS, deferred pass only (the stream has drained): [S0Q2_WAVES][32 rows][S0_LDS_STRIDE] floats
+    size_t stage_wave = 32 * S0_LDS_STRIDE;                  // (floats)
+    size_t flist = c.take<uint16_t>(S0Q2_WAVES * S0Q2_FCAP); // [S0Q2_WAVES][S0Q2_FCAP] flagged-tile entries
+    size_t flist_wave = S0Q2_FCAP;                           // (entries)
+    size_t bytes = c.bytes;
+};
+static_assert(s0q2_lds{}.stage + S0Q2_WAVES * s0q2_lds{}.stage_wave * sizeof(float) <= s0q2_lds{}.flist, "the staging rows fit inside the tile buffers they alias");
+static_assert(S0Q2_WAVES != 8 || S0Q2_SBT != 4 || s0q2_lds{}.bytes == 139264, "s0_centroid_scores_qs2's dynamic LDS");
+static_assert(s0q2_lds{}.bytes <= FLMR_LDS_CU_BYTES, "s0_centroid_scores_qs2: one workgroup per CU (no static LDS)");
+
 template <bool HI_ONLY>
 __global__ __launch_bounds__(64 * S0Q2_WAVES, 1) void s0_centroid_scores_qs2(flmr_s0_args a, int rows_per_slice) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 31, h = lane >> 5;
-    float* stage = reinterpret_cast<float*>(smem) + wave * 32 * S0_LDS_STRIDE;   // deferred pass only: aliases the tile buffers
-    char* const abuf = smem;
-    uint16_t* const flist = reinterpret_cast<uint16_t*>(abuf + S0Q2_NBUF * S0Q2_SBT * 8192) + wave * S0Q2_FCAP;
+    constexpr s0q2_lds L;
+    float* stage = reinterpret_cast<float*>(smem + L.stage) + wave * L.stage_wave;   // deferred pass only: aliases the tile buffers
+    char* const abuf = smem + L.abuf;
+    uint16_t* const flist = reinterpret_cast<uint16_t*>(smem + L.flist) + wave * L.flist_wave;
     const uint32_t abuf_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)abuf);
     const int row_begin = blockIdx.y * rows_per_slice;
     const int row_end = row_begin + rows_per_slice < a.K ? row_begin + rows_per_slice : a.K;  // multiples of 64
@@ -736,7 +775,7 @@ __global__ __launch_bounds__(64 * S0Q2_WAVES, 1) void s0_centroid_scores_qs2(flm
 #pragma unroll
         for (int u = 0; u < S0Q2_SBT; u++) {
             const uint32_t voff = (uint32_t)(row_begin + 32 * S0Q2_SBT * pp + 32 * u + prow) * 256u + poff;  // K * 256 < 4 GB (launcher)
-            const uint32_t dst = __builtin_amdgcn_readfirstlane(abuf_lds + ((p % S0Q2_NBUF) * S0Q2_SBT + u) * 8192 + wave * 1024);
+            const uint32_t dst = __builtin_amdgcn_readfirstlane(abuf_lds + ((p % S0Q2_NBUF) * S0Q2_SBT + u) * S0_TILE_BYTES + wave * 1024);
             asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" ::"v"(voff), "s"(dst), "s"(a.centroids_f16) : "memory", "m0");
         }
     };
@@ -796,7 +835,7 @@ __global__ __launch_bounds__(64 * S0Q2_WAVES, 1) void s0_centroid_scores_qs2(flm
 #pragma unroll
     for (int q = 0; q < S0Q_QT; q++) { gmax[q] = FLMR_NEG_INF; cmax[q] = FLMR_NEG_INF; flag[q] = 0ull; }
     auto fetch = [&](f16x8 (&av)[8], int buf_tile) {   // buf_tile = (super-block % NBUF) * SBT + tile
-        const char* const pt_ = abuf + __builtin_amdgcn_readfirstlane(buf_tile * 8192);
+        const char* const pt_ = abuf + __builtin_amdgcn_readfirstlane(buf_tile * S0_TILE_BYTES);
 #pragma unroll
         for (int s = 0; s < 8; s++) av[s] = *reinterpret_cast<const f16x8*>(pt_ + aoff[s]);
     };
@@ -806,7 +845,7 @@ __global__ __launch_bounds__(64 * S0Q2_WAVES, 1) void s0_centroid_scores_qs2(flm
     auto seg = [&](auto mm_c, auto epi_c, auto end_c, const f16x8 (&av)[8], f16x8 (&avn)[8], int next_buf_tile, f32x16 (&an)[S0Q_QT],
                    const f32x16 (&ao)[S0Q_QT], int blk) {
         constexpr bool MM = decltype(mm_c)::value, EPI = decltype(epi_c)::value, END = decltype(end_c)::value;
-        const char* const pn = abuf + __builtin_amdgcn_readfirstlane(next_buf_tile * 8192);
+        const char* const pn = abuf + __builtin_amdgcn_readfirstlane(next_buf_tile * S0_TILE_BYTES);
         float m[S0Q_QT];
 #pragma unroll
         for (int s = 0; s < 8; s++) {
@@ -1300,11 +1339,11 @@ static int launch_s0_t(const flmr_s0_args& a, s0_form form, hipStream_t st) {
         if (slices < 1) slices = 1;
         const int rows_per_slice = (int)flmr_round_up(flmr_ceil_div(a.K, slices), 64);
         slices = (int)flmr_ceil_div(a.K, rows_per_slice);
-        const size_t ldsq = (size_t)8 * 32 * S0_LDS_STRIDE * sizeof(float) + (size_t)S0Q_NBUF * 2 * 8192;
+        const size_t ldsq = s0q_lds{}.bytes;
         // (the idx words were cleared and the bounds of this batch's queries written by s0_prepare_kernel above)
         if (form == s0_form::qs2) {
             if (!(a.q_hi_only || a.q_err) || a.K % (32 * S0Q2_SBT) != 0) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the qs2 stage 0 needs hi-first bounds and K %% %d == 0", 32 * S0Q2_SBT);
-            const size_t ldsq2 = (size_t)S0Q2_NBUF * S0Q2_SBT * 8192 + (size_t)S0Q2_WAVES * S0Q2_FCAP * sizeof(uint16_t);
+            const size_t ldsq2 = s0q2_lds{}.bytes;
             const int ngroups2 = (int)flmr_ceil_div(a.nqueries, S0Q2_WAVES * S0Q_QT);
             int slices2 = 512 / ngroups2;   // (rounded down: a few workgroups over 2 x 256 would cost a third round)
             if (slices2 > a.K / (32 * S0Q2_SBT)) slices2 = a.K / (32 * S0Q2_SBT);
@@ -1350,7 +1389,7 @@ static int launch_s0_t(const flmr_s0_args& a, s0_form form, hipStream_t st) {
         if (a.q_err) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "the row-stationary stage 0 leaves no hi-first bounds");
         hipLaunchKernelGGL(s0_split_q, dim3((a.ncol * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens,
                            a.nq, a.nq_cand, a.ncol, a.q_hi, a.q_lo, a.q_hi_only);
-        const size_t lds = (size_t)S0_WAVES * 32 * S0_LDS_STRIDE * sizeof(float) + (S0_DMA_B ? (size_t)2 * S0_DCH * 2 * 8192 : (size_t)S0_CH * 2 * 32 * S0_BROW * sizeof(_Float16));
+        const size_t lds = s0_f16_lds{}.bytes;
         const dim3 grid((a.nblk + S0_WAVES - 1) / S0_WAVES, qsplit), block(64 * S0_WAVES);
         if (form == s0_form::f16_sparse) {
             FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_f16<false, true>),
@@ -1411,7 +1450,7 @@ int flmr_launch_centroid_argmax(flmr_s0_args a, int32_t* out_codes, hipStream_t 
     const int qsplit = a.nqueries < 8 ? a.nqueries : 8;
     hipLaunchKernelGGL(s0_split_q, dim3((a.ncol * FLMR_DIM + 255) / 256, a.nqueries), dim3(256), 0, st, a.Q, a.q_lens, a.nq,
                        a.nq_cand, a.ncol, a.q_hi, a.q_lo, a.q_hi_only);
-    const size_t lds = (size_t)S0_WAVES * 32 * S0_LDS_STRIDE * sizeof(float) + (S0_DMA_B ? (size_t)2 * S0_DCH * 2 * 8192 : (size_t)S0_CH * 2 * 32 * S0_BROW * sizeof(_Float16));
+    const size_t lds = s0_f16_lds{}.bytes;
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(s0_centroid_scores_f16<true, true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((s0_centroid_scores_f16<true, true>), dim3((a.nblk + S0_WAVES - 1) / S0_WAVES, qsplit), dim3(64 * S0_WAVES), lds, st, a);

@@ -130,6 +130,21 @@ __device__ __forceinline__ uint32_t d1_push_bit(uint32_t hm, uint32_t x) { retur
 // LPC lanes per candidate x CPL codes per lane (16 x 4, 16 x 8 or 32 x 8 by the index's usual number of distinct codes per passage).
 // Every load of the round loop is compiler-visible and UNCONDITIONAL (s1_exact_kernel's header says why): the two code buffers'
 // requests are then the only vector-memory operations in flight and the compiler's wait at the top of a round is a vmcnt(CPL / 4).
+// (lpc, cpl: the kernel's LPC, CPL.  Align 1 throughout: every size is padded to its successor's alignment where it is stated, and
+// rounding a runtime offset again costs the kernel instructions.)
+struct d1i_lds {
+    int nqueries, idx_words, lpc, cpl, img_rows;
+    flmr_lds c;
+    size_t scan_list = c.take<int>((nqueries + 3) & ~3, 1);        // the queries that take this pass
+    size_t lbits = c.take<uint32_t>(idx_words, 1);                 // the query's centroid mask
+    size_t lpre = c.take<uint16_t>((idx_words + 7) & ~7, 1);       // its prefix counts (padded to 16 B)
+    int list_wave = (64 / lpc) * (lpc * cpl) + 64;                 // (u16 entries) R * LISTCAP + one scratch entry per lane
+    size_t lists = c.take<uint16_t>(D1_WAVES * list_wave, 1);      // [D1_WAVES][list_wave] hit lists
+    size_t img = c.take<char>((img_rows + 1) * 64, 1);     // [img_rows + the padding row][64 B] fp16 score-row images; = the bytes before them
+    size_t bytes = c.bytes;
+};
+static_assert(d1i_lds{256, 4096, 16, 4, 1000}.bytes == 99904, "s1_image_kernel's dynamic LDS: 256 queries, K = 131072, 16 x 4, 1000 image rows");
+
 template <int LPC, int CPL>
 __global__ __launch_bounds__(D1_THREADS) void s1_image_kernel(flmr_s1d_args a) {
     constexpr int R = 64 / LPC;            // candidates per round
@@ -148,13 +163,13 @@ __global__ __launch_bounds__(D1_THREADS) void s1_image_kernel(flmr_s1d_args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int sub = lane / LPC, l = lane % LPC;
     const int hg = l / LPR, pr = l % LPR;
-    // LDS: [scan list: nqueries i32][bits: idx_words u32][prefix: idx_words u16 (padded to 16 B)][lists: per wave R * LISTCAP + 64 u16][images]
-    int* scan_list = reinterpret_cast<int*>(smem);
-    uint32_t* lbits = reinterpret_cast<uint32_t*>(scan_list + ((a.nqueries + 3) & ~3));
-    uint16_t* lpre = reinterpret_cast<uint16_t*>(lbits + a.idx_words);
-    uint16_t* lists = lpre + ((a.idx_words + 7) & ~7);
-    uint16_t* my_list = lists + (size_t)wave * (R * LISTCAP + 64);   // (+ one scratch entry per lane)
-    char* img = reinterpret_cast<char*>(lists + (size_t)D1_WAVES * (R * LISTCAP + 64));
+    const d1i_lds L{a.nqueries, a.idx_words, LPC, CPL, a.img_rows};
+    int* scan_list = reinterpret_cast<int*>(smem + L.scan_list);
+    uint32_t* lbits = flmr_lds_next<uint32_t>(scan_list, L.scan_list, L.lbits);
+    uint16_t* lpre = flmr_lds_next<uint16_t>(lbits, L.lbits, L.lpre);
+    uint16_t* lists = flmr_lds_next<uint16_t>(lpre, L.lpre, L.lists);
+    uint16_t* my_list = lists + (size_t)wave * L.list_wave;
+    char* img = flmr_lds_next<char>(lists, L.lists, L.img);
 
     if (a.any && a.any[0] == 0) return;   // (uniform: no query of the batch takes this pass)
     if (tid == 0) s_nscan = 0;
@@ -453,6 +468,25 @@ __global__ __launch_bounds__(D1_THREADS) void s1_image_kernel(flmr_s1d_args a) {
 #define D1X_GROUP 32   // candidates per wave and group (the LDS table holds 32 x 36 floats per wave)
 #define D1X_TRS 36
 
+// (the mask first: its address is then a compile-time offset of the probes; a word and the rank of its first bit side by side: one
+// 8-byte read per hit in the walk.  No static __shared__ in this kernel: the dynamic block -- the mask -- then starts at LDS address 0
+// and a probe's address is the shifted code itself; the block scan's scratch and two scalars sit behind the stash.  Align 1: see d1i_lds.)
+struct d1x_lds {
+    int nqueries, idx_words, lpc, cpl, group;
+    flmr_lds c;
+    size_t ltab = c.take<uint2>(idx_words, 1);                     // mask + ranks: idx_words x {u32, u32}
+    size_t scan_list = c.take<int>((nqueries + 3) & ~3, 1);        // the queries that take this pass
+    int list_wave = (64 / lpc) * (lpc * cpl);                      // (u16 entries) R * LISTCAP
+    size_t lists = c.take<uint16_t>(D1_WAVES * list_wave, 1);      // [D1_WAVES][list_wave] hit lists
+    size_t tr_wave = (size_t)group * D1X_TRS;                      // (floats)
+    size_t tr = c.take<float>(D1_WAVES * tr_wave, 1);              // [D1_WAVES][group][D1X_TRS] transposed column maxima
+    int stash_wave = cpl * 64;                                     // (ints)
+    size_t stash = c.take<int>(D1_WAVES * stash_wave, 1);          // [D1_WAVES][CPL][64] a lane's codes of the round, [code][lane]
+    size_t scan_lds = c.take<int>(32, 1);                          // the block scan's scratch [17], s_nscan, s_item
+    size_t bytes = c.bytes;
+};
+static_assert(d1x_lds{256, 4096, 16, 4, 32}.bytes == 132224, "s1_exact_kernel's dynamic LDS: 256 queries, K = 131072, 16 x 4, groups of 32");
+
 template <int LPC, int CPL>
 __global__ __launch_bounds__(D1_THREADS) void s1_exact_kernel(flmr_s1d_args a) {
     constexpr int R = 64 / LPC;            // candidates per round
@@ -466,23 +500,19 @@ __global__ __launch_bounds__(D1_THREADS) void s1_exact_kernel(flmr_s1d_args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int sub = lane / LPC, l = lane % LPC;
     const int hg = l / LPR, pr = l % LPR;
-    // LDS: [mask + ranks: idx_words x {u32, u32}][scan list][lists: per wave R * LISTCAP u16][tr: per wave a.group x D1X_TRS f32][stash: per wave CPL x 64 i32]
-    // (the mask first: its address is then a compile-time offset of the probes; a word and the rank of its first bit side by side:
-    // one 8-byte read per hit in the walk)
-    uint2* ltab = reinterpret_cast<uint2*>(smem);
-    const uint32_t ltab_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-    int* scan_list = reinterpret_cast<int*>(ltab + a.idx_words);
-    uint16_t* lists = reinterpret_cast<uint16_t*>(scan_list + ((a.nqueries + 3) & ~3));
-    uint16_t* my_list = lists + (size_t)wave * (R * LISTCAP);
-    float* tr = reinterpret_cast<float*>(lists + (size_t)D1_WAVES * (R * LISTCAP)) + (size_t)wave * a.group * D1X_TRS;
+    const d1x_lds L{a.nqueries, a.idx_words, LPC, CPL, a.group};
+    uint2* ltab = reinterpret_cast<uint2*>(smem + L.ltab);
+    const uint32_t ltab_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)(smem + L.ltab));
+    int* scan_list = flmr_lds_next<int>(ltab, L.ltab, L.scan_list);
+    uint16_t* lists = flmr_lds_next<uint16_t>(scan_list, L.scan_list, L.lists);
+    uint16_t* my_list = lists + (size_t)wave * L.list_wave;
+    float* const tr0 = flmr_lds_next<float>(lists, L.lists, L.tr);
+    float* tr = tr0 + wave * L.tr_wave;
     // a lane's codes of the round, [code][lane]: the hit walk reads code e of its lane with one LDS load (a register array
     // indexed by a lane's own e is a chain of CPL compare-and-selects)
-    int* stash = reinterpret_cast<int*>(reinterpret_cast<float*>(lists + (size_t)D1_WAVES * (R * LISTCAP)) + (size_t)D1_WAVES * a.group * D1X_TRS) +
-                 (size_t)wave * (CPL * 64) + lane;
-    // (no static __shared__ in this kernel: the dynamic block -- the mask -- then starts at LDS address 0 and a probe's address is
-    // the shifted code itself; the block scan's scratch and two scalars sit behind the stash)
-    int* const scan_lds = reinterpret_cast<int*>(reinterpret_cast<float*>(lists + (size_t)D1_WAVES * (R * LISTCAP)) + (size_t)D1_WAVES * a.group * D1X_TRS) +
-                          (size_t)D1_WAVES * (CPL * 64);
+    int* const stash0 = flmr_lds_next<int>(tr0, L.tr, L.stash);
+    int* stash = stash0 + (size_t)wave * L.stash_wave + lane;
+    int* const scan_lds = flmr_lds_next<int>(stash0, L.stash, L.scan_lds);
     int& s_nscan = scan_lds[17];
     int& s_item = scan_lds[18];
 
@@ -796,10 +826,6 @@ static void d1_shape(double mean_codes, int* lpc, int* cpl) {
     *lpc = mean_codes > 144.0 ? 32 : 16;
     *cpl = mean_codes > 72.0 ? 8 : 4;
 }
-static size_t d1x_lds(int nqueries, int idx_words, int lpc, int cpl, int group) {
-    return (size_t)((nqueries + 3) & ~3) * 4 + (size_t)idx_words * 8 +
-           (size_t)D1_WAVES * (64 / lpc) * (lpc * cpl) * 2 + (size_t)D1_WAVES * group * D1X_TRS * 4 + (size_t)D1_WAVES * cpl * 64 * 4 + 32 * 4;
-}
 
 // the exact pass: (lanes per candidate, codes per lane) by the index's usual number of distinct codes per passage
 int flmr_launch_s1_exact(const flmr_s1d_args& a_in, double mean_codes, hipStream_t st) {
@@ -807,8 +833,8 @@ int flmr_launch_s1_exact(const flmr_s1d_args& a_in, double mean_codes, hipStream
     int lpc, cpl;
     d1_shape(mean_codes, &lpc, &cpl);
     // candidates per wave and group: 32 where the table fits (and the caller does not ask for 16), else 16
-    a.group = (a.group == 16 || d1x_lds(a.nqueries, a.idx_words, lpc, cpl, D1X_GROUP) > (size_t)160 * 1024 - 1024) ? 16 : D1X_GROUP;
-    const size_t lds = d1x_lds(a.nqueries, a.idx_words, lpc, cpl, a.group);
+    a.group = (a.group == 16 || d1x_lds{a.nqueries, a.idx_words, lpc, cpl, D1X_GROUP}.bytes > (size_t)160 * 1024 - 1024) ? 16 : D1X_GROUP;
+    const size_t lds = d1x_lds{a.nqueries, a.idx_words, lpc, cpl, a.group}.bytes;
     if (lds > (size_t)160 * 1024 - 1024) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dense stage 1: K = %d does not fit the LDS form", a.idx_words * 32);
     if (a.codes_len > 0xffffffffLL) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dense stage 1: token offsets beyond 32 bits");
     if (a.parts < 1) a.parts = 8;
@@ -827,17 +853,13 @@ int flmr_launch_s1_exact(const flmr_s1d_args& a_in, double mean_codes, hipStream
     return FLMR_OK;
 }
 
-// LDS the image launch needs besides the images; rows of images that fit beside it
-static size_t d1_fixed_lds(int nqueries, int idx_words, int lpc, int cpl) {
-    return (size_t)((nqueries + 3) & ~3) * 4 + (size_t)idx_words * 4 + (size_t)((idx_words + 7) & ~7) * 2 +
-           (size_t)D1_WAVES * ((64 / lpc) * (lpc * cpl) + 64) * 2;
-}
+// rows of images that fit beside the rest of the image launch's LDS (d1i_lds::img)
 int flmr_s1_dense_image_rows(int nqueries, int idx_words, double mean_codes) {
     int lpc, cpl;
     d1_shape(mean_codes, &lpc, &cpl);
     const size_t budget = (size_t)160 * 1024 - 1024;   // static __shared__ of the kernel and alignment
-    const size_t fixed = d1_fixed_lds(nqueries, idx_words, lpc, cpl);
-    if (fixed + 64 * 65 > budget || d1x_lds(nqueries, idx_words, lpc, cpl, 16) > budget) return 0;
+    const size_t fixed = d1i_lds{nqueries, idx_words, lpc, cpl, 0}.img;
+    if (fixed + 64 * 65 > budget || d1x_lds{nqueries, idx_words, lpc, cpl, 16}.bytes > budget) return 0;
     const size_t rows = (budget - fixed) / 64 - 1;   // (+ the padding row)
     return (int)(rows > 65000 ? 65000 : rows);
 }
@@ -848,7 +870,7 @@ int flmr_launch_s1_image(const flmr_s1d_args& a_in, double mean_codes, hipStream
     d1_shape(mean_codes, &lpc, &cpl);
     a.img_rows = flmr_s1_dense_image_rows(a.nqueries, a.idx_words, mean_codes);
     if (a.img_rows < 1) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dense stage 1: the centroid mask leaves no room for score-row images in LDS");
-    const size_t lds = d1_fixed_lds(a.nqueries, a.idx_words, lpc, cpl) + (size_t)(a.img_rows + 1) * 64;
+    const size_t lds = d1i_lds{a.nqueries, a.idx_words, lpc, cpl, a.img_rows}.bytes;
     if (a.codes_len > 0xffffffffLL) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "dense stage 1: token offsets beyond 32 bits");
     if (a.parts < 1) a.parts = 4;
     int64_t grid = 256;   // one persistent workgroup per CU; a multiple of 8 so that workgroup L and its items share L % 8

@@ -70,6 +70,14 @@ __device__ __forceinline__ float w2_dec(int e) { return __int_as_float(e ^ ((e >
 #define W2_DOCS (W2_WAVES * 128)     // passages per work item: two per lane
 #define W2_BUF ((W2_SLICE + 1) * W2_STRIDE)   // words per buffer: the score rows + one dummy row (the smallest image)
 #define W2_INF 0x7fffffff
+struct w2_lds {
+    flmr_lds c;
+    size_t buf = c.take<int>(W2_BUF);         // [W2_SLICE + 1][W2_STRIDE] score images (w2_enc)
+    size_t blds = c.take<w2h8>(8 * 64);       // [8 steps][64 lanes] q_lo in MFMA order
+    size_t bytes = c.bytes;
+};
+static_assert(w2_lds{}.bytes == 155792, "filter_stage2_walk_kernel's dynamic LDS");
+static_assert(w2_lds{}.bytes <= FLMR_LDS_CU_BYTES, "filter_stage2_walk_kernel: one workgroup per CU (no static LDS)");
 #define W2_MAX_DOCLEN FLMR_SORTED_MAX_DOCLEN   // longest passage the in-LDS code sort handles
 
 // ------------------------------------------------------------------------------------------------
@@ -218,8 +226,9 @@ __global__ __launch_bounds__(64 * W2_WAVES, 2) void filter_stage2_walk_kernel(
     long long prof_acc[3] = {0, 0, 0};
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* const buf = reinterpret_cast<int*>(smem);  // [W2_SLICE + 1][W2_STRIDE] score images (w2_enc)
-    w2h8* const blds = reinterpret_cast<w2h8*>(smem + (size_t)W2_BUF * sizeof(int));  // [8 steps][64 lanes] q_lo in MFMA order
+    constexpr w2_lds L;
+    int* const buf = reinterpret_cast<int*>(smem + L.buf);
+    w2h8* const blds = reinterpret_cast<w2h8*>(smem + L.blds);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
     const int K = f.K;
@@ -477,7 +486,7 @@ int flmr_launch_filter_stage2_walk(const flmr_filter_args& f, const int32_t* pid
     const int nchunks = (int)flmr_ceil_div(max_count, W2_DOCS);
     const int64_t nitems = (int64_t)f.nqueries * nchunks;
     const int grid = (int)(nitems < cu_count() ? nitems : cu_count());
-    const size_t lds = (size_t)W2_BUF * sizeof(int) + 8192;
+    const size_t lds = w2_lds{}.bytes;
     FLMR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(filter_stage2_walk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(filter_stage2_walk_kernel, dim3(grid), dim3(64 * W2_WAVES), lds, st, f, pids, pid_stride, counts, keys,
                        key_stride, cen16_tiled, q_hi, q_lo, codes_sorted, nchunks, (int)nitems

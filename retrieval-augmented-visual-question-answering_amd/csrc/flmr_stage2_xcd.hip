@@ -36,7 +36,19 @@
 #define X2_AHEAD 6  // the codes of a tile are requested six tiles before its rows are consumed (four before they are requested)
 #define X2_RING 8   // code ring slots (256 B each) per wave
 #define X2_OCT 256  // octets (of 8 tokens) per batch of passages: the per-wave octet table
-#define X2_WAVE_LDS (16384 + X2_RING * 256 + X2_OCT * 6)  // row buffers + code ring + octet table
+// dynamic LDS, wave-major: region r of wave w at w * wave + r
+struct x2_lds {
+    flmr_lds c;
+    int rowbuf_tile = 32 * FLMR_DIM * sizeof(_Float16);     // a tile's 32 centroid rows x 256 B
+    size_t rowbuf = c.take<char>(2 * rowbuf_tile);          // tiles t and t + 1
+    size_t ring = c.take<char>(X2_RING * 64 * sizeof(int32_t));   // code ring: X2_RING tiles, one dword per lane
+    size_t opos = c.take<uint32_t>(X2_OCT);                 // octet table: position of the octet's first token
+    size_t ometa = c.take<uint16_t>(X2_OCT);                // (tokens in the octet - 1) | passage lane << 3
+    size_t wave = c.bytes;
+    size_t bytes = X2_WAVES * wave;
+};
+static_assert(x2_lds{}.wave == 19968 && x2_lds{}.bytes == 79872, "filter_stage2_xcd_kernel's dynamic LDS");
+static_assert(2 * x2_lds{}.bytes <= FLMR_LDS_CU_BYTES, "filter_stage2_xcd_kernel: two workgroups per CU (no static LDS)");
 
 typedef _Float16 x2h8 __attribute__((ext_vector_type(8)));
 typedef float x2f16 __attribute__((ext_vector_type(16)));
@@ -190,16 +202,15 @@ __global__ __launch_bounds__(256, 2) void filter_stage2_xcd_kernel(flmr_filter_a
     const int slot0 = (g * X2_WAVES + wave) * X2_DOCS;
     if (slot0 >= cnt) return;  // (no block-wide barrier below)
     const int nd = cnt - slot0 < X2_DOCS ? cnt - slot0 : X2_DOCS;
-    // per wave: row buffers 2 x 8 KB | code ring 8 x 256 B | octet table: position of the octet's first token (u32) [X2_OCT],
-    // then (tokens in the octet - 1) | passage lane << 3 (u16) [X2_OCT]
-    char* const wbase = smem + (size_t)wave * X2_WAVE_LDS;
-    char* const rowbuf = wbase;
-    char* const ring = wbase + 16384;
-    uint32_t* const opos = reinterpret_cast<uint32_t*>(wbase + 16384 + X2_RING * 256);
-    uint16_t* const ometa = reinterpret_cast<uint16_t*>(wbase + 16384 + X2_RING * 256 + X2_OCT * 4);
+    constexpr x2_lds lay;
+    char* const wbase = smem + (size_t)wave * lay.wave;
+    char* const rowbuf = wbase + lay.rowbuf;
+    char* const ring = wbase + lay.ring;
+    uint32_t* const opos = reinterpret_cast<uint32_t*>(wbase + lay.opos);
+    uint16_t* const ometa = reinterpret_cast<uint16_t*>(wbase + lay.ometa);
     const uint32_t rowbuf_lds =
         __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)rowbuf);
-    const uint32_t ring_lds = rowbuf_lds + 16384;
+    const uint32_t ring_lds = rowbuf_lds + (uint32_t)(lay.ring - lay.rowbuf);
 
     // ---- this lane's passage: its run of slice-`sl` tokens in the sorted copy ----
     int run_len = 0;
@@ -292,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void filter_stage2_xcd_kernel(flmr_filter_a
                 for (int gq = 0; gq < 8; gq++) c[gq] = cr[4 * gq];
 #pragma unroll
                 for (int gq = 0; gq < 8; gq++) {
-                    const uint32_t dst = rowbuf_lds + (t & 1) * 8192 + gq * 1024;
+                    const uint32_t dst = rowbuf_lds + (t & 1) * lay.rowbuf_tile + gq * 1024;
                     uint32_t voff;
                     asm volatile("s_mov_b32 m0, %2\n\tv_lshl_add_u32 %0, %3, 8, %4\n\tglobal_load_lds_dwordx4 %0, %1"
                                  : "=&v"(voff)
@@ -330,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void filter_stage2_xcd_kernel(flmr_filter_a
                 x2h8 av[8];
 #pragma unroll
                 for (int s = 0; s < 8; s++)
-                    av[s] = *reinterpret_cast<const x2h8*>(rowbuf + (t & 1) * 8192 + i * 256 + (((8 * h + s) ^ (i & 15)) << 4));
+                    av[s] = *reinterpret_cast<const x2h8*>(rowbuf + (t & 1) * lay.rowbuf_tile + i * 256 + (((8 * h + s) ^ (i & 15)) << 4));
                 int om;  // lanes 0..3: passage lane of octets 4t .. 4t+3
                 {
                     int o = 4 * t + (lane & 3);
@@ -356,7 +367,7 @@ __global__ __launch_bounds__(256, 2) void filter_stage2_xcd_kernel(flmr_filter_a
 #if !defined(X2_LATE_DMA) && !defined(X2_NO_DMA)
 #pragma unroll
                 for (int gq = 0; gq < 8; gq++) {
-                    const uint32_t dst = rowbuf_lds + (t & 1) * 8192 + gq * 1024;
+                    const uint32_t dst = rowbuf_lds + (t & 1) * lay.rowbuf_tile + gq * 1024;
                     uint32_t voff;
                     asm volatile("s_mov_b32 m0, %2\n\tv_lshl_add_u32 %0, %3, 8, %4\n\tglobal_load_lds_dwordx4 %0, %1"
                                  : "=&v"(voff)
@@ -426,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void filter_stage2_xcd_kernel(flmr_filter_a
 #ifdef X2_LATE_DMA   // development form: the row pieces of tile t+2 issued in the fold's VALU-only stretches, two per octet
 #pragma unroll
                     for (int gq = 2 * k; gq < 2 * k + 2; gq++) {
-                        const uint32_t dst = rowbuf_lds + (t & 1) * 8192 + gq * 1024;
+                        const uint32_t dst = rowbuf_lds + (t & 1) * lay.rowbuf_tile + gq * 1024;
                         uint32_t voff;
                         asm volatile("s_mov_b32 m0, %2\n\tv_lshl_add_u32 %0, %3, 8, %4\n\tglobal_load_lds_dwordx4 %0, %1"
                                      : "=&v"(voff)
@@ -470,7 +481,15 @@ __global__ __launch_bounds__(256, 2) void filter_stage2_xcd_kernel(flmr_filter_a
 #ifndef X2_REG_MINW
 #define X2_REG_MINW 2
 #endif
-#define X2R_WAVE_LDS (8192 + X2_OCT * 6)   // transit buffer + octet table
+struct x2r_lds {   // wave-major, like x2_lds
+    flmr_lds c;
+    size_t transit = c.take<char>(32 * FLMR_DIM * sizeof(_Float16));   // the tile being consumed
+    size_t opos = c.take<uint32_t>(X2_OCT);
+    size_t ometa = c.take<uint16_t>(X2_OCT);
+    size_t wave = c.bytes;
+    size_t bytes = X2_WAVES * wave;
+};
+static_assert(x2r_lds{}.wave == 9728 && x2r_lds{}.bytes == 38912, "filter_stage2_xreg_kernel's dynamic LDS per wave");
 template <bool HI_ONLY>
 __global__ __launch_bounds__(256, X2_REG_MINW) void filter_stage2_xreg_kernel(flmr_filter_args f, const int32_t* __restrict__ pids, int64_t pid_stride,
                                                                                const int32_t* __restrict__ counts, float* __restrict__ part,
@@ -492,10 +511,11 @@ __global__ __launch_bounds__(256, X2_REG_MINW) void filter_stage2_xreg_kernel(fl
     const int slot0 = (g * X2_WAVES + wave) * X2_DOCS;
     if (slot0 >= cnt) return;
     const int nd = cnt - slot0 < X2_DOCS ? cnt - slot0 : X2_DOCS;
-    char* const wbase = smem + (size_t)wave * X2R_WAVE_LDS;
-    char* const transit = wbase;
-    uint32_t* const opos = reinterpret_cast<uint32_t*>(wbase + 8192);
-    uint16_t* const ometa = reinterpret_cast<uint16_t*>(wbase + 8192 + X2_OCT * 4);
+    constexpr x2r_lds lay;
+    char* const wbase = smem + (size_t)wave * lay.wave;
+    char* const transit = wbase + lay.transit;
+    uint32_t* const opos = reinterpret_cast<uint32_t*>(wbase + lay.opos);
+    uint16_t* const ometa = reinterpret_cast<uint16_t*>(wbase + lay.ometa);
     int run_len = 0;
     uint32_t run_base = 0;
     if (lane < nd) {
@@ -727,13 +747,13 @@ int flmr_launch_filter_stage2_xcd_ex(const flmr_filter_args& f, const int32_t* p
     const int64_t grid = (int64_t)nsl * f.nqueries * G;
     if (grid > 0x7fffffffLL) FLMR_FAIL(FLMR_ERR_UNSUPPORTED, "stage-2 grid too large");
 #ifdef X2_ROWS_IN_REGS
-    const size_t lds = (size_t)X2_WAVES * X2R_WAVE_LDS;
+    const size_t lds = x2r_lds{}.bytes;
 #define X2_KERNEL filter_stage2_xreg_kernel
 #elif defined(X2_LDS_PAD)   // development probe: a larger request leaves one workgroup per CU (half the tiles in flight, one wave per SIMD)
-    const size_t lds = (size_t)X2_WAVES * X2_WAVE_LDS + X2_LDS_PAD;
+    const size_t lds = x2_lds{}.bytes + X2_LDS_PAD;
 #define X2_KERNEL filter_stage2_xcd_kernel
 #else
-    const size_t lds = (size_t)X2_WAVES * X2_WAVE_LDS;
+    const size_t lds = x2_lds{}.bytes;
 #define X2_KERNEL filter_stage2_xcd_kernel
 #endif
     if (hi_only) {
